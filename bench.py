@@ -11,6 +11,12 @@ A "step" = one pass of the trainable hot path over one synthetic batch of 8 scen
 heads -> loss -> backward -> one RCCL gradient all-reduce -> clip -> AdamW.  The frozen,
 no_grad image stream is outside the path; its output pyramid is a resident input.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (plus, with
+``--dump-outputs DIR``, what the last timed step computed as DIR/<name>.npy).  ``--full`` adds
+everything else the line can carry: the stability repeats, the eager kernel-timer pass and the
+roofline objects, the collective's own time, the live PMC passes, the secondary legs and the CPU
+baseline (each still switched off by its own --no-* option).
 """
 import argparse
 import json
@@ -94,9 +100,9 @@ def pmc_live(args):
         for c in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(scratch, c)
             cmd = ["rocprofv3", "--pmc", c, "--output-format", "csv", "-d", d, "-o", "p", "--", sys.executable,
-                   os.path.abspath(__file__), "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-secondary",
-                   "--dtype", args.dtype, "--batch", str(args.batch), "--msda-points", str(args.msda_points),
-                   "--cloud", args.cloud, "--no-pmc-live"]
+                   os.path.abspath(__file__), "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline",
+                   "--no-secondary", "--dtype", args.dtype, "--batch", str(args.batch), "--msda-points",
+                   str(args.msda_points), "--cloud", args.cloud, "--no-pmc-live"]
             subprocess.run(cmd, cwd="/tmp", env=env, timeout=150, capture_output=True, check=True)
             hits = glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)
             if not hits:
@@ -298,6 +304,29 @@ def cpu_baseline(seconds_budget=20.0):
                                              min_ms=1e3 * min(tc), median_ms=1e3 * float(np.median(tc)))})
 
 
+def dump_outputs(path, trainer, model, loss):
+    """--dump-outputs: what one step of the timed path hands its caller, as <path>/<name>.npy (float32):
+    loss (its total loss), grads (the flat gradient buffer the update read), params (every trainable
+    parameter after the update, flat, in the optimizer's order) and buffers (the floating-point buffers -
+    BatchNorm running statistics - flat, in named_buffers() order).
+    The step is the last timed one - the same step function on the same batch - run once more after the timing,
+    from the seeded state the run began with.  The training loop's own state after the timed steps differs from
+    run to run: the float atomics' rounding (about 1e-6 of the gradient) becomes whole AdamW steps of lr on the
+    gradients that are rounding noise, and the untrained network turns those into different gradients within
+    two steps.  From the seeded state the step's inputs are identical from run to run, so two builds can be
+    compared output for output."""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    bufs = [b.detach().reshape(-1).float() for _, b in model.named_buffers() if b.is_floating_point()]
+    arrays = {"loss": loss.detach().reshape(-1).float(),
+              "grads": trainer.flat.flat,
+              "params": trainer.opt.flat if trainer.fused else
+              torch.cat([p.detach().reshape(-1) for p in trainer.flat.params]),
+              "buffers": torch.cat(bufs) if bufs else torch.zeros(0)}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def sa_path_ms(model, device, B, seed=0):
     """BASELINE configs[1]: the PointNet++ SA path alone (FPS / ball query / grouping + the shared MLPs
     of the 4 SA + 2 FP levels), fp32, pre-pass NOT pipelined (every pass pays its own FPS chain):
@@ -375,10 +404,20 @@ def main():
                          "7.2: 5.15 vs 5.01 ms - a third active hardware queue costs more than the 0.1 ms it hides)")
     ap.add_argument("--no-pmc-live", action="store_true",
                     help="read the HBM traffic fields from the committed profiles/ instead of re-measuring them with "
-                         "two rocprofv3 --pmc passes of this command (default at one GPU, ~10 s; falls back to the "
+                         "two rocprofv3 --pmc passes of this command (default of --full at one GPU, ~10 s; falls back to the "
                          "committed files on any failure)")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary legs (resident / bf16 / P=4 / clustered / B=16 step times, SA path)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the two repeat passes, the eager kernel-timer pass and the roofline "
+                         "objects, the collective's own time (more than one rank or --allreduce-stub-us), the live "
+                         "PMC passes, the secondary legs and the CPU baseline.  Off: the run only sets up, warms up, "
+                         "times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the last timed step once more from the seeded state the run "
+                         "began with and write what it computed - its total loss, the flat gradient buffer, the "
+                         "updated parameters and the floating-point buffers (BatchNorm statistics) - as "
+                         "DIR/<name>.npy in float32 (about 18 MB at the default size); rank 0 writes")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -426,14 +465,21 @@ def main():
                           gt_counts=None if i == 0 else cnt_rng.integers(0, MAX_GT + 1, size=args.batch))[0]
                for i in range(NB)]
     batch = batches[0]
+    # --dump-outputs: the seeded state the run begins with (model, AdamW moments and step count, dropout counter),
+    # taken before the capture's warm-up steps update it - see dump_outputs
+    seeded = None
+    if args.dump_outputs:
+        seeded = trainer.state_dict()
+        seeded["model"] = {k: v.detach().clone() for k, v in seeded["model"].items()}
 
-    fps_timer = KernelTimer(ops, "furthest_point_sample")
-    # the longest launch on the critical path (the FPS chain runs underneath the step on a side stream):
-    # SA1's last shared-MLP layer backward, and its forward twin
-    from demf_amd import _ffi
     sa1_rows = args.batch * 2048 * 64
-    mlp_timer = FfiTimer(_ffi, "demf_mlp_bwd_pool", (sa1_rows, 128, 64, 64))
-    fwd_timer = FfiTimer(_ffi, "demf_mlp_gemm_fwd_pool_bn_st", (sa1_rows, 64, 128))
+    if args.full:
+        fps_timer = KernelTimer(ops, "furthest_point_sample")
+        # the longest launch on the critical path (the FPS chain runs underneath the step on a side stream):
+        # SA1's last shared-MLP layer backward, and its forward twin
+        from demf_amd import _ffi
+        mlp_timer = FfiTimer(_ffi, "demf_mlp_bwd_pool", (sa1_rows, 128, 64, 64))
+        fwd_timer = FfiTimer(_ffi, "demf_mlp_gemm_fwd_pool_bn_st", (sa1_rows, 64, 128))
 
     def sync():
         if world > 1:
@@ -485,6 +531,90 @@ def main():
         step()
     sync()
     elapsed = time.perf_counter() - t0
+    trainer.flush()               # (overlapped collective: the last step's norm + AdamW are still owed)
+    # a throughput figure over non-finite arithmetic would be meaningless: refuse to report it
+    if not bool(torch.isfinite(trainer.flat.flat).all()) or \
+            not all(bool(torch.isfinite(p).all()) for p in model.parameters()):
+        raise RuntimeError("non-finite gradients/parameters after the timed steps")
+    rank_info = None
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=device)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = t.item()
+        # what makes the ranks different replicas of one job: their data seeds and dropout streams
+        from demf_amd import fused
+        rank_info = [None] * world
+        dist.all_gather_object(rank_info, dict(rank=rank, batch_seeds=[1000 + rank + 7919 * i for i in range(NB)],
+                                               dropout_seed=fused.get_rng_state(device)[0]))
+    if args.dump_outputs:
+        # the last timed step once more, from the seeded state: the same step function on the same batch (the loop's
+        # counter stepped back by one), so that its inputs are identical from run to run (see dump_outputs)
+        trainer.load_state_dict(seeded)
+        k[0] -= 1
+        loss = step()
+        sync()
+        trainer.flush()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, trainer, model, loss)
+
+    out = None
+    if rank == 0:
+        scenes = args.batch * world * args.steps
+        ms_step = 1000.0 * elapsed / args.steps
+        two_graphs = bool(os.environ.get("DEMF_GEO_AT_BWD"))
+        if args.no_graph:
+            launch = "eager"
+        else:
+            launch = ("hipGraphs(fwd+loss | bwd), pre-pass of the next batch launched in between" if two_graphs
+                      else "one hipGraph(fwd+loss+bwd), pre-pass of the next batch launched in front of it") + \
+                " on a side stream; " + ("norm + clip + AdamW inside the graph"
+                                         if getattr(replay, "update_in_graph", False)
+                                         else "eager allreduce / clip / AdamW behind it")
+        out = {
+            "metric": "DeMF fusion fwd+bwd scenes/sec at 20k pts + 530x730 RGB",
+            "value": scenes / elapsed, "unit": "scenes/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_step, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None,
+            "dtype": "bf16" if args.dtype == "bf16" else "f32", "data": "synthetic",
+            # fp32 RESULTS; in the default mode the shared-MLP products are issued as 3-term bf16
+            # splits on the bf16 MFMA (emulated fp32, error vs fp64 = the fp32 MFMA's)
+            "emulated_fp32": args.dtype in ("f32", "f32x3") and MFMA_PATH[args.dtype] in (MFMA_PATH["f32x3"], MFMA_PATH["f32h2"]),
+            "config": {"workload": "BASELINE configs[2]: full DeMF fusion hot path fwd+loss+bwd+"
+                                   "allreduce+AdamW, %d scenes/GPU x (20000 pts, 800x1120 -> "
+                                   "4-level 256-ch pyramid), 256 queries, H=8 L=4 P=%d, %s"
+                                   % (args.batch, args.msda_points,
+                                      "fp32" if args.dtype != "bf16" else
+                                      "bf16 MFMA / fp32 accumulate+storage (BASELINE configs[3] per GPU)"),
+                       "compute_mode": args.dtype, "mfma_path": MFMA_PATH[args.dtype],
+                       "scenes_per_gpu": args.batch, "parallelism": f"dp{world}",
+                       "cloud": args.cloud,
+                       "timed_loop": ("one resident batch replayed" if args.resident else
+                                      "%d distinct HBM-resident batches cycled through replay.load(): target "
+                                      "padding, meta refresh, static-buffer copies and the next cloud's "
+                                      "pre-pass are inside the timed step" % NB) +
+                                     ("; double-buffered static inputs: batch k+1 is loaded on an input stream "
+                                      "while step k runs" if (not args.resident and replay2 is not None) else ""),
+                       "launch": launch},
+        }
+        w_, stub_, ov_ = trainer.allreduce_config()
+        out["allreduce"] = {
+            "buckets_bytes": [int(trainer.flat.flat.numel()) * 4], "collective": "one flat all-reduce (SUM), "
+            "1/world folded into AdamW", "world": w_, "stub_us": stub_, "overlap": bool(ov_),
+            "overlap_how": "issued on a communication stream behind the step's graph; norm + AdamW are enqueued at "
+                           "the start of the next step, so the collective runs underneath the next batch's input "
+                           "path (replay.load) and pre-pass launch" if ov_ else None,
+            "us": None}
+        if rank_info is not None:
+            out["ranks"] = [dict(rank=r["rank"], batch_seeds=r["batch_seeds"], dropout_seed=r["dropout_seed"])
+                            for r in rank_info]
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     repeats = []
     for _ in range(2):
         sync()
@@ -494,10 +624,6 @@ def main():
         sync()
         repeats.append(1000.0 * (time.perf_counter() - t1) / args.steps)
     trainer.flush()               # (overlapped collective: the last step's norm + AdamW are still owed)
-    # a throughput figure over non-finite arithmetic would be meaningless: refuse to report it
-    if not bool(torch.isfinite(trainer.flat.flat).all()) or \
-            not all(bool(torch.isfinite(p).all()) for p in model.parameters()):
-        raise RuntimeError("non-finite gradients/parameters after the timed steps")
     # the collective's own time (HIP events around the all-reduce of the flat 8.76 MB buffer)
     allreduce_us = None
     if world > 1 or args.allreduce_stub_us > 0:
@@ -594,12 +720,12 @@ def main():
             # its own process, as a user would run it (measured inside this one - after the other models,
             # graphs and static buffers - the same replay came out 40 % slower: 11.2 vs 7.7 ms)
             import subprocess
-            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--batch", "16", "--steps", str(args.steps),
+            r16 = subprocess.run([sys.executable, os.path.abspath(__file__), "--batch", "16", "--steps", str(args.steps),
                                   "--warmup", str(args.warmup), "--dtype", args.dtype, "--msda-points",
                                   str(args.msda_points), "--no-secondary", "--no-cpu-baseline", "--no-pmc-live"],
                                  capture_output=True, text=True, timeout=600)
             try:
-                d16 = json.loads(out.stdout.strip().splitlines()[-1])
+                d16 = json.loads(r16.stdout.strip().splitlines()[-1])
                 secondary["b16_ms_per_step"] = d16["ms_per_step"]
                 secondary["b16_scenes_per_s"] = d16["value"]
             except Exception:
@@ -691,8 +817,8 @@ def main():
                 env2.update(DEMF_SHARE_DEVICE="1", DEMF_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0",
                             MASTER_PORT=port, OMP_NUM_THREADS="4")
                 r2 = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "2", "--steps", "5", "--warmup",
-                                     "2", "--batch", "4", "--dtype", args.dtype], env=env2, capture_output=True,
-                                    text=True, timeout=300)
+                                     "2", "--batch", "4", "--dtype", args.dtype, "--full"], env=env2,
+                                    capture_output=True, text=True, timeout=300)
                 line = [l for l in r2.stdout.splitlines() if l.startswith("{")]
                 if r2.returncode == 0 and line:
                     o2 = json.loads(line[-1])
@@ -704,73 +830,14 @@ def main():
                     secondary["world2_shared_gpu"] = {"error": (r2.stderr or r2.stdout)[-300:]}
             except Exception as exc:      # (a secondary figure must not take the headline line down with it)
                 secondary["world2_shared_gpu"] = {"error": repr(exc)[:200]}
-    rank_info = None
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=device)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = t.item()
-        # what makes the ranks different replicas of one job: their data seeds and dropout streams
-        from demf_amd import fused
-        rank_info = [None] * world
-        dist.all_gather_object(rank_info, dict(rank=rank, batch_seeds=[1000 + rank + 7919 * i for i in range(NB)],
-                                               dropout_seed=fused.get_rng_state(device)[0]))
-
     if rank == 0:
-        scenes = args.batch * world * args.steps
-        ms_step = 1000.0 * elapsed / args.steps
-        two_graphs = bool(os.environ.get("DEMF_GEO_AT_BWD"))
-        if args.no_graph:
-            launch = "eager"
-        else:
-            launch = ("hipGraphs(fwd+loss | bwd), pre-pass of the next batch launched in between" if two_graphs
-                      else "one hipGraph(fwd+loss+bwd), pre-pass of the next batch launched in front of it") + \
-                " on a side stream; " + ("norm + clip + AdamW inside the graph"
-                                         if getattr(replay, "update_in_graph", False)
-                                         else "eager allreduce / clip / AdamW behind it")
-        out = {
-            "metric": "DeMF fusion fwd+bwd scenes/sec at 20k pts + 530x730 RGB",
-            "value": scenes / elapsed, "unit": "scenes/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_step, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16" if args.dtype == "bf16" else "f32", "data": "synthetic",
-            # fp32 RESULTS; in the default mode the shared-MLP products are issued as 3-term bf16
-            # splits on the bf16 MFMA (emulated fp32, error vs fp64 = the fp32 MFMA's)
-            "emulated_fp32": args.dtype in ("f32", "f32x3") and MFMA_PATH[args.dtype] in (MFMA_PATH["f32x3"], MFMA_PATH["f32h2"]),
-            "config": {"workload": "BASELINE configs[2]: full DeMF fusion hot path fwd+loss+bwd+"
-                                   "allreduce+AdamW, %d scenes/GPU x (20000 pts, 800x1120 -> "
-                                   "4-level 256-ch pyramid), 256 queries, H=8 L=4 P=%d, %s"
-                                   % (args.batch, args.msda_points,
-                                      "fp32" if args.dtype != "bf16" else
-                                      "bf16 MFMA / fp32 accumulate+storage (BASELINE configs[3] per GPU)"),
-                       "compute_mode": args.dtype, "mfma_path": MFMA_PATH[args.dtype],
-                       "scenes_per_gpu": args.batch, "parallelism": f"dp{world}",
-                       "cloud": args.cloud,
-                       "timed_loop": ("one resident batch replayed" if args.resident else
-                                      "%d distinct HBM-resident batches cycled through replay.load(): target "
-                                      "padding, meta refresh, static-buffer copies and the next cloud's "
-                                      "pre-pass are inside the timed step" % NB) +
-                                     ("; double-buffered static inputs: batch k+1 is loaded on an input stream "
-                                      "while step k runs" if (not args.resident and replay2 is not None) else ""),
-                       "launch": launch},
-            # two more passes of the same K steps right after the timed region (stability check;
-            # `value` is the first, contract-shaped region only)
-            "repeat_ms_per_step": repeats,
-        }
+        # two more passes of the same K steps right after the timed region (stability check;
+        # `value` is the first, contract-shaped region only)
+        out["repeat_ms_per_step"] = repeats
         if allreduce_us is not None:
             # HIP events around the one all-reduce of the flat 8.76 MB gradient buffer (rank 0's view)
             out["allreduce_us"] = allreduce_us
-        w_, stub_, ov_ = trainer.allreduce_config()
-        out["allreduce"] = {
-            "buckets_bytes": [int(trainer.flat.flat.numel()) * 4], "collective": "one flat all-reduce (SUM), "
-            "1/world folded into AdamW", "world": w_, "stub_us": stub_, "overlap": bool(ov_),
-            "overlap_how": "issued on a communication stream behind the step's graph; norm + AdamW are enqueued at "
-                           "the start of the next step, so the collective runs underneath the next batch's input "
-                           "path (replay.load) and pre-pass launch" if ov_ else None,
-            "us": allreduce_us}
-        if rank_info is not None:
-            out["ranks"] = [dict(rank=r["rank"], batch_seeds=r["batch_seeds"], dropout_seed=r["dropout_seed"])
-                            for r in rank_info]
+            out["allreduce"]["us"] = allreduce_us
         # ---- headline roofline: the longest launch ON the step's main stream - SA1's last layer backward.
         # Algorithmic bytes of that layer's backward = read the (R,64) input rows once, write their (R,64)
         # gradient once, read the pooled gradient, its argmax rows and the raw pooled values (3 x (R/64,128)

@@ -274,7 +274,7 @@ def train_conditioned_weights(cfg, log=None):
 
 
 def conditioned_goldens():
-    """Third head golden (tests/golden/ref_head_cond.npz): the REAL reference head (+ restated backbone) in
+    """Third head golden (tests/golden/ref_head_cond.npz + ref_head_cond_grad.npz): the REAL reference head (+ restated backbone) in
     train mode on CONDITIONED weights - train_conditioned_weights above - and a held-out seeded batch: every
     forward output, the targets, the losses and EVERY parameter gradient, plus the weights themselves (``w.<key>``;
     they are the result of an optimisation run, not of a seed).  On a trained-like network the discrete events of
@@ -291,8 +291,41 @@ def conditioned_goldens():
     return out
 
 
+# the reference config values tests/test_config_vs_reference.py holds demf_amd/config.py to:
+# config file (under configs/) -> the top-level names the test reads from it
+CONFIG_NAMES = {"demf/demf_votenet.py": ("model", "optimizer"),
+                "_base_/schedules/schedule_3x.py": ("lr", "optimizer_config", "lr_config"),
+                "deformdetr/imvotenet_image.py": ("model",)}
+
+
+def _tag_tuples(v):
+    """A config value in JSON form; tuples stay distinct from lists as {"__tuple__": [...]}."""
+    if isinstance(v, tuple):
+        return {"__tuple__": [_tag_tuples(x) for x in v]}
+    if isinstance(v, list):
+        return [_tag_tuples(x) for x in v]
+    if isinstance(v, dict):
+        return {k: _tag_tuples(x) for k, x in v.items()}
+    return v
+
+
+def config_goldens():
+    """The reference's config files (plain Python dict files) executed, and the values of CONFIG_NAMES kept."""
+    out = {}
+    for rel, names in CONFIG_NAMES.items():
+        ns = {}
+        with open(os.path.join(shim.REF, "configs", rel)) as f:
+            exec(compile(f.read(), rel, "exec"), ns)
+        out[rel] = {k: _tag_tuples(ns[k]) for k in names}
+    return out
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
+    import json
+    with open(os.path.join(GOLD, "ref_config.json"), "w") as f:
+        json.dump(config_goldens(), f, indent=1)
+        f.write("\n")
     cfg = fixtures.tiny_cfg()
     for name, seed, B, n_gt in (("tiny_a", 1, 2, 4), ("tiny_b", 2, 3, 2)):
         batch = fixtures.make_scene_batch(B, 1024, fixtures.TINY_PYRAMID, fixtures.TINY_INPUT,
@@ -304,7 +337,12 @@ def main():
     np.savez_compressed(os.path.join(GOLD, "ref_bboxes.npz"), **bbox_goldens())
     np.savez_compressed(os.path.join(GOLD, "ref_encoder.npz"), **encoder_goldens())
     np.savez_compressed(os.path.join(GOLD, "ref_encoder256.npz"), **encoder256_goldens())
-    np.savez_compressed(os.path.join(GOLD, "ref_head_cond.npz"), **conditioned_goldens())
+    cond = conditioned_goldens()
+    # two files, each under the 1 MiB a committed file may hold: the parameter gradients go to the second
+    # (tests/helpers.py load_golden merges them back)
+    grads = {k: cond.pop(k) for k in list(cond) if k.startswith("grad.")}
+    np.savez_compressed(os.path.join(GOLD, "ref_head_cond.npz"), **cond)
+    np.savez_compressed(os.path.join(GOLD, "ref_head_cond_grad.npz"), **grads)
     print("golden vectors written to", GOLD)
 
 

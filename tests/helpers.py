@@ -1,4 +1,6 @@
 """Shared synthetic-input builders for the test-suite (seeded, size-parametrised)."""
+import os
+
 import numpy as np
 
 # reference pyramid for an 800x1120 padded input
@@ -45,3 +47,23 @@ def msda_inputs(B, Q, H, Dh, shapes, P, seed=0, spread=0.25, dtype=np.float32):
     shp = np.asarray(shapes, np.int64)
     return (value.astype(dtype), shp, level_start_index(shapes), loc.astype(dtype),
             attw.astype(dtype))
+
+
+class Golden(dict):
+    """The arrays of a golden file by name, read like np.load's NpzFile: gold[name], gold.files."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
+def load_golden(golden_dir, name):
+    """tests/golden/<name>.npz, with the arrays of <name>_grad.npz merged in where that second part exists (a
+    golden too large for one committed file keeps its parameter gradients, the grad.* arrays, there)."""
+    gold = Golden()
+    for part in (name + ".npz", name + "_grad.npz"):
+        path = os.path.join(golden_dir, part)
+        if part == name + ".npz" or os.path.exists(path):
+            with np.load(path) as z:
+                gold.update((k, z[k]) for k in z.files)
+    return gold

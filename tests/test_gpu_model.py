@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import parity_tools as P
+from helpers import load_golden
 from oracle import fixtures
 
 pytestmark = pytest.mark.gpu
@@ -104,7 +105,7 @@ def test_hot_path_vs_real_reference_goldens(name, seed, B, n_gt, golden_dir):
 def test_hot_path_on_conditioned_weights(golden_dir, graph):
     """The north-star bars WITHOUT a seed qualification: on conditioned (trained-like) weights - 200 AdamW steps
     of the fp64 oracle at the tiny config, committed with the REAL reference head's outputs on a held-out batch
-    (tests/golden/ref_head_cond.npz, oracle/pin_reference.py: conditioned_goldens; the CPU fp32 oracle reproduces
+    (tests/golden/ref_head_cond{,_grad}.npz, oracle/pin_reference.py: conditioned_goldens; the CPU fp32 oracle reproduces
     that golden to round-off, tests/test_oracle_model.py) - the HIP path is held to
         1e-4 (absolute, x max(1, tensor scale)) on every forward tensor up to and including EVERY decode output,
         bit-exact indices and integer targets, 1e-4 relative on every loss term,
@@ -114,7 +115,7 @@ def test_hot_path_on_conditioned_weights(golden_dir, graph):
     hipGraph of forward + loss + backward (what bench.py times)."""
     from demf_amd.modules import DeMFHotPath
     from oracle.pin_reference import COND as c
-    gold = np.load(os.path.join(golden_dir, "ref_head_cond.npz"))
+    gold = load_golden(golden_dir, "ref_head_cond")
     cfg = fixtures.tiny_cfg()
     batch = fixtures.make_scene_batch(c["B"], c["N"], fixtures.TINY_PYRAMID, fixtures.TINY_INPUT,
                                       cfg.head.embed_dims, seed=c["eval_seed"], n_gt=c["n_gt"])

@@ -137,7 +137,7 @@ def test_plain_bench_launches_its_own_ranks():
 def test_bench_eight_ranks_on_one_gpu():
     """The driver's 8-GPU launch line, eight ranks sharing one GPU through gloo (one scene per rank):
     JSON shape, n_gpus, the weak-scaling arithmetic (value = all ranks' scenes over the max-over-ranks
-    time), the all-reduce's own time, and that the eight replicas differ where they must - data seeds and
+    time), the all-reduce's own time (measured with --full), and that the eight replicas differ where they must - data seeds and
     dropout streams - while the reference's launcher gives every rank its own shard
     (tools/dist_train.sh:8-9, train.py:56-63)."""
     env = dict(os.environ, DEMF_SHARE_DEVICE="1", DEMF_DIST_BACKEND="gloo",
@@ -145,7 +145,7 @@ def test_bench_eight_ranks_on_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "2",
-           "--batch", "1"]
+           "--batch", "1", "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

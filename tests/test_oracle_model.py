@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import load_golden
 from oracle import deps, fixtures
 from oracle.model import Coder, OracleDeMF, PositionEmbeddingLearned
 
@@ -160,7 +161,7 @@ def test_oracle_encoder_vs_real_encoder_at_the_reference_shape(golden_dir):
 
 
 def test_oracle_vs_real_head_on_conditioned_weights(golden_dir):
-    """tests/golden/ref_head_cond.npz: the REAL reference head on CONDITIONED weights (200 AdamW steps of the fp64
+    """tests/golden/ref_head_cond.npz (+ ref_head_cond_grad.npz): the REAL reference head on CONDITIONED weights (200 AdamW steps of the fp64
     oracle, oracle/pin_reference.py: conditioned_goldens) and a held-out batch.  The fp32 oracle reproduces its decode
     outputs, losses and EVERY parameter gradient to fp32 round-off - the pin of the checker the GPU test
     (tests/test_gpu_model.py: test_hot_path_on_conditioned_weights) then leans on."""
@@ -170,7 +171,7 @@ def test_oracle_vs_real_head_on_conditioned_weights(golden_dir):
     from oracle import fixtures
     from oracle.model import OracleDeMF
     from oracle.pin_reference import COND as c
-    gold = np.load(os.path.join(golden_dir, "ref_head_cond.npz"))
+    gold = load_golden(golden_dir, "ref_head_cond")
     cfg = fixtures.tiny_cfg()
     batch = fixtures.make_scene_batch(c["B"], c["N"], fixtures.TINY_PYRAMID, fixtures.TINY_INPUT,
                                       cfg.head.embed_dims, seed=c["eval_seed"], n_gt=c["n_gt"])

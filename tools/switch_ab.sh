@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of the round's kernel-form switches on the resident step (bench.py --resident): one line per setting.
-# usage (GPU box, repo root): bash tools/switch_ab.sh > gpurun_out/<tag>_switch_ab.txt
-run() { python bench.py --resident --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%-62s %.3f ms  (repeats %.3f %.3f)' % ('$1', d['ms_per_step'], *d['repeat_ms_per_step']))"; }
+# usage (repo root): bash tools/switch_ab.sh > prof_out/<tag>_switch_ab.txt
+run() { python bench.py --resident --full --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%-62s %.3f ms  (repeats %.3f %.3f)' % ('$1', d['ms_per_step'], *d['repeat_ms_per_step']))"; }
 run "defaults"
 DEMF_F16_TERMS=0 run "DEMF_F16_TERMS=0 (three bf16 terms everywhere)"
 DEMF_F16_TERMS_BWD=0 run "DEMF_F16_TERMS_BWD=0 (two fp16 terms in the forward kernels only)"
