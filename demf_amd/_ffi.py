@@ -54,6 +54,9 @@ SIGNATURES = {
     "demf_vote_targets": [_c_int] * 4 + [_ptr] * 8,
     "demf_box_extent_count": [_c_int] * 4 + [_ptr] * 8,
     "demf_aligned_nms": [_c_int, _c_int, _c_float] + [_ptr] * 6,
+    "demf_box3d_iou": [_c_int, _c_int] + [_ptr] * 4,
+    "demf_eval_match": [_c_int, _c_int, _ptr, _c_int, _c_int] + [_ptr] * 7,
+    "demf_eval_ap": [_c_int, _c_int] + [_ptr] * 8,
     "demf_proposal_targets": [_c_int] * 4 + [_c_float] * 3 + [_ptr] * 18,
     "demf_gt_prep": [_c_int] * 3 + [_ptr] * 10,
     "demf_pad_gt": [_c_int] * 2 + [_ptr] * 8,

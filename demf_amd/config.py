@@ -117,3 +117,7 @@ def head_kwargs(cfg: DeMFCfg):
 IMG_SHAPE = (800, 1102, 3)
 BATCH_INPUT_SHAPE = (800, 1120)
 PYRAMID_SHAPES = ((100, 140), (50, 70), (25, 35), (13, 18))
+
+# configs/_base_/datasets/sunrgbd-3d-10class.py:3-4: the label -> name map of the SUN RGB-D evaluation
+SUNRGBD_CLASSES = ('bed', 'table', 'sofa', 'chair', 'toilet', 'desk', 'dresser', 'night_stand', 'bookshelf',
+                   'bathtub')

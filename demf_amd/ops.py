@@ -1963,6 +1963,62 @@ def aligned_nms(extent, scores, classes, valid, iou_thr):
     return keep.bool()
 
 
+# --------------------------------------------------------------------------
+# Indoor detection evaluation (csrc/eval3d.hip; evaluation.indoor_eval composes these)
+# --------------------------------------------------------------------------
+EVAL_MAX_PRED_PER_SEGMENT = 4096
+EVAL_MAX_GT_PER_SEGMENT = 256
+
+
+def box3d_overlaps(boxes1, boxes2):
+    """mmdet3d BaseInstance3DBoxes.overlaps(boxes1, boxes2, mode='iou') for depth boxes: (N,7) x (M,7)
+    bottom-centre (x, y, z_bottom, dx, dy, dz, yaw) -> (N,M) 3D IoU of the rotated boxes (fp32)."""
+    _chk(boxes1, "boxes1")
+    _chk(boxes2, "boxes2")
+    if boxes1.dim() != 2 or boxes1.shape[1] != 7 or boxes2.dim() != 2 or boxes2.shape[1] != 7:
+        raise ValueError(f"box3d_overlaps takes (N,7) and (M,7) boxes, got {tuple(boxes1.shape)} and "
+                         f"{tuple(boxes2.shape)}")
+    N, M = boxes1.shape[0], boxes2.shape[0]
+    iou = torch.empty((N, M), dtype=torch.float32, device=boxes1.device)
+    _ffi.call("demf_box3d_iou", N, M, _p(boxes1), _p(boxes2), _p(iou), _stream())
+    return iou
+
+
+def eval_match(pred_boxes, order, pred_off, gt_boxes, gt_off, thresholds, max_pred, max_gt):
+    """Greedy TP/FP matching of eval_det_cls per (class, scene) segment (see demf_eval_match):
+    pred_boxes (P,7), order (P,) int32 (segment-major, score-descending caller rows), pred_off / gt_off (S+1,)
+    int32, gt_boxes (G,7) grouped by segment; max_pred / max_gt: the largest segment (host ints).
+    -> tp (P,T) uint8 in pred_boxes' row order."""
+    _chk(pred_boxes, "pred_boxes")
+    _chk(order, "order", torch.int32)
+    _chk(pred_off, "pred_off", torch.int32)
+    _chk(gt_boxes, "gt_boxes")
+    _chk(gt_off, "gt_off", torch.int32)
+    T = len(thresholds)
+    thr = (ctypes.c_float * max(T, 1))(*[float(t) for t in thresholds])
+    tp = torch.zeros((pred_boxes.shape[0], T), dtype=torch.uint8, device=pred_boxes.device)
+    _ffi.call("demf_eval_match", pred_off.numel() - 1, T, thr, int(max_pred), int(max_gt), _p(pred_boxes),
+              _p(order), _p(pred_off), _p(gt_boxes), _p(gt_off), _p(tp), _stream())
+    return tp
+
+
+def eval_ap(tp_sorted, cls_off, npos, ws_off, total_npos):
+    """VOC-area AP and final recall per (class, threshold) (see demf_eval_ap): tp_sorted (P,T) uint8 in
+    class-major global score order, cls_off (C+1,), npos (C,), ws_off (C+1,) = prefix sums of npos, int32;
+    total_npos = ws_off[-1] as a host int.  -> ap, rec (C,T) float64; NaN where npos is 0."""
+    _chk(tp_sorted, "tp_sorted", torch.uint8)
+    _chk(cls_off, "cls_off", torch.int32)
+    _chk(npos, "npos", torch.int32)
+    _chk(ws_off, "ws_off", torch.int32)
+    C, T = npos.numel(), tp_sorted.shape[1]
+    dev = tp_sorted.device
+    out = torch.empty((2, C, T), dtype=torch.float64, device=dev)
+    ws = torch.empty((int(total_npos) * T,), dtype=torch.int32, device=dev)
+    _ffi.call("demf_eval_ap", C, T, _p(cls_off), _p(npos), _p(ws_off), _p(tp_sorted), _p(ws), _p(out[0]),
+              _p(out[1]), _stream())
+    return out[0], out[1]
+
+
 def sa_index_chain(N, level_indices):
     """[arange(N) per scene] + every SA level's samples as int64 indices into the input cloud (the
     ``sa_indices`` of PointNet2SASSG.forward) from the levels' int32 FPS indices, one launch."""

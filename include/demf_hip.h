@@ -768,6 +768,34 @@ DEMF_INTERNAL int demf_aligned_nms(int B, int K, float iou_thr, const float* ext
                      demf_stream_t stream);
 
 /* ------------------------------------------------------------------ *
+ * Indoor detection evaluation (csrc/eval3d.hip): mmdet3d 0.18.1 indoor_eval as SUNRGBDDataset.evaluate
+ * calls it for `eval.py --eval mAP` (configs/_base_/datasets/sunrgbd-3d-10class.py:107).
+ * Boxes are the bottom-centre form (x, y, z_bottom, dx, dy, dz, yaw); IoU arithmetic fp32.
+ * ------------------------------------------------------------------ */
+
+/* iou (N,M) = BaseInstance3DBoxes.overlaps(boxes1 (N,7), boxes2 (M,7), mode='iou') of depth boxes: rotated
+ * footprint intersection x height overlap / max(vol1 + vol2 - inter, 1e-8).                              */
+DEMF_INTERNAL int demf_box3d_iou(int N, int M, const float* boxes1, const float* boxes2, float* iou,
+                   demf_stream_t stream);
+
+/* Greedy matching of eval_det_cls over S (class, scene) segments.  Segment s: the detections
+ * order[pred_off[s] .. pred_off[s+1]) (caller rows of pred_boxes, score-descending) and the ground truth
+ * gt_boxes rows gt_off[s] .. gt_off[s+1) in that scene's order.  thresholds: T <= 4 IoU thresholds in HOST
+ * memory.  tp (P,T) bytes in the caller's row order: 1 iff the row's best GT (first maximum) has
+ * IoU > threshold and no earlier detection of the segment took it.  max_pred / max_gt: the largest segment;
+ * above 4096 detections or 256 GT the call returns DEMF_EUNSUPPORTED.                                    */
+DEMF_INTERNAL int demf_eval_match(int S, int T, const float* thresholds, int max_pred, int max_gt,
+                    const float* pred_boxes, const int* order, const int* pred_off, const float* gt_boxes,
+                    const int* gt_off, unsigned char* tp, demf_stream_t stream);
+
+/* VOC-area average precision and final recall per (class, threshold) -> ap, rec (C,T) doubles.  tp_sorted
+ * (P,T) bytes: class c's flags are rows cls_off[c] .. cls_off[c+1) in that class's global score order.
+ * npos (C): ground-truth count per class (0 -> NaN, upstream's 0/0); ws_off (C+1): prefix sums of npos;
+ * workspace: ws_off[C] * T ints.  tp_sorted / workspace may be null when they hold no element.            */
+DEMF_INTERNAL int demf_eval_ap(int C, int T, const int* cls_off, const int* npos, const int* ws_off,
+                 const unsigned char* tp_sorted, int* workspace, double* ap, double* rec, demf_stream_t stream);
+
+/* ------------------------------------------------------------------ *
  * Optimizer step on flat buffers: torch.optim.AdamW + clip_grad_norm_ as the reference's
  * runner applies them (configs/_base_/schedules/schedule_3x.py:6-7: AdamW lr 0.008, wd 0.01,
  * grad_clip max_norm 10; configs/demf/demf_votenet.py:16-24: 'decoder' lr_mult 0.05).  One call
