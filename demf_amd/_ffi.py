@@ -57,6 +57,9 @@ SIGNATURES = {
     "demf_box3d_iou": [_c_int, _c_int] + [_ptr] * 4,
     "demf_eval_match": [_c_int, _c_int, _ptr, _c_int, _c_int] + [_ptr] * 7,
     "demf_eval_ap": [_c_int, _c_int] + [_ptr] * 8,
+    "demf_points_floor": [_c_int, _c_int, ctypes.c_longlong] + [_ptr] * 4,
+    "demf_points_prep": [_c_int] * 3 + [ctypes.c_longlong] + [_ptr] * 8,
+    "demf_image_prep": [_c_int] * 3 + [ctypes.c_longlong] + [_ptr] * 6,
     "demf_proposal_targets": [_c_int] * 4 + [_c_float] * 3 + [_ptr] * 18,
     "demf_gt_prep": [_c_int] * 3 + [_ptr] * 10,
     "demf_pad_gt": [_c_int] * 2 + [_ptr] * 8,

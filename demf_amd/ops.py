@@ -2019,6 +2019,89 @@ def eval_ap(tp_sorted, cls_off, npos, ws_off, total_npos):
     return out[0], out[1]
 
 
+# --------------------------------------------------------------------------
+# Input pipeline (csrc/pipeline.hip): ragged raw scenes -> the detector's points / img tensors
+# --------------------------------------------------------------------------
+IMG_NORM = ((123.675, 116.28, 103.53), (58.395, 57.12, 57.375))     # demf_votenet.py img_norm_cfg (RGB order)
+
+
+def _chk_raw_points(raw, offsets):
+    _chk(raw, "raw")
+    _chk(offsets, "offsets", torch.int64)
+    if raw.dim() != 2 or raw.shape[1] < 3 or raw.shape[0] == 0:
+        raise ValueError(f"raw must be (total, load_dim >= 3) records with total > 0, got {tuple(raw.shape)}")
+    if offsets.dim() != 1 or offsets.numel() < 2:
+        raise ValueError(f"offsets must be (B+1,) with B >= 1, got {tuple(offsets.shape)}")
+    if offsets.device != raw.device:
+        raise ValueError("raw and offsets must be on the same device")
+
+
+def points_floor(raw, offsets):
+    """np.percentile(z, 0.99) per scene (LoadPointsFromFile(shift_height=True)'s floor): raw (total, load_dim) fp32
+    records of B scenes concatenated, offsets (B+1,) int64 record offsets -> (B,) fp32."""
+    _chk_raw_points(raw, offsets)
+    B = offsets.numel() - 1
+    out = torch.empty((B,), dtype=torch.float32, device=raw.device)
+    _ffi.call("demf_points_floor", B, raw.shape[1], raw.shape[0], _p(raw), _p(offsets), _p(out), _stream())
+    return out
+
+
+def points_prep(raw, offsets, floor, params, seeds, num_points, return_index=False, out=None, index=None):
+    """RandomFlip3D + GlobalRotScaleTrans + PointSample on the raw records (see demf_points_prep): floor (B,) from
+    points_floor, params (B,8) fp32 [flip, cos, sin, scale, tx, ty, tz, -], seeds (B,) int64 ->
+    points (B, num_points, 4) fp32 [+ the (B, num_points) int32 source index within each scene]."""
+    _chk_raw_points(raw, offsets)
+    B = offsets.numel() - 1
+    _chk(floor, "floor")
+    _chk(params, "params")
+    _chk(seeds, "seeds", torch.int64)
+    if floor.shape != (B,) or params.shape != (B, 8) or seeds.shape != (B,):
+        raise ValueError(f"floor (B,), params (B,8), seeds (B,) for B = {B}, got {tuple(floor.shape)}, "
+                         f"{tuple(params.shape)}, {tuple(seeds.shape)}")
+    if int(num_points) <= 0:
+        raise ValueError("num_points must be positive")
+    if out is None:
+        out = torch.empty((B, int(num_points), 4), dtype=torch.float32, device=raw.device)
+    _chk(out, "out")
+    if out.shape != (B, int(num_points), 4):
+        raise ValueError(f"out must be {(B, int(num_points), 4)}, got {tuple(out.shape)}")
+    if return_index and index is None:
+        index = torch.empty((B, int(num_points)), dtype=torch.int32, device=raw.device)
+    if index is not None:
+        _chk(index, "index", torch.int32)
+    _ffi.call("demf_points_prep", B, int(num_points), raw.shape[1], raw.shape[0], _p(raw), _p(offsets), _p(floor),
+              _p(params), _p(seeds), _p(out), _p(index), _stream())
+    return (out, index) if return_index else out
+
+
+def image_prep(src, offsets, shapes, pad_shape, mean=IMG_NORM[0], std=IMG_NORM[1], out=None):
+    """Resize + Normalize + Pad + collate (see demf_image_prep): src (bytes,) uint8 = the scenes' HWC RGB images
+    concatenated, offsets (B+1,) int64 byte offsets, shapes (B,4) int32 (h_in, w_in, h_out, w_out), pad_shape =
+    (Hp, Wp) of the batch (Wp % 4 == 0) -> (B, 3, Hp, Wp) fp32.  mmcv imrescale (cv2 INTER_LINEAR source coordinates)
+    -> uint8 rounding -> Normalize -> zero padding [dep-recall].  Not bit-exact to cv2: its fixed-point path can
+    differ by one level from this fp32 interpolation; cv2 is not installed here, so that difference is unpinned."""
+    _chk(src, "src", torch.uint8)
+    _chk(offsets, "offsets", torch.int64)
+    _chk(shapes, "shapes", torch.int32)
+    if src.dim() != 1 or src.numel() == 0:
+        raise ValueError(f"src must be a non-empty flat uint8 buffer, got {tuple(src.shape)}")
+    B = offsets.numel() - 1
+    if B < 1 or shapes.shape != (B, 4):
+        raise ValueError(f"offsets (B+1,) with B >= 1 and shapes (B,4), got {tuple(offsets.shape)}, "
+                         f"{tuple(shapes.shape)}")
+    Hp, Wp = int(pad_shape[0]), int(pad_shape[1])
+    if Hp <= 0 or Wp <= 0 or Wp % 4:
+        raise ValueError(f"pad_shape must be positive with a width divisible by 4, got {(Hp, Wp)}")
+    if out is None:
+        out = torch.empty((B, 3, Hp, Wp), dtype=torch.float32, device=src.device)
+    _chk(out, "out")
+    if out.shape != (B, 3, Hp, Wp):
+        raise ValueError(f"out must be {(B, 3, Hp, Wp)}, got {tuple(out.shape)}")
+    ms = (ctypes.c_float * 6)(*[float(v) for v in tuple(mean) + tuple(std)])
+    _ffi.call("demf_image_prep", B, Hp, Wp, src.numel(), _p(src), _p(offsets), _p(shapes), ms, _p(out), _stream())
+    return out
+
+
 def sa_index_chain(N, level_indices):
     """[arange(N) per scene] + every SA level's samples as int64 indices into the input cloud (the
     ``sa_indices`` of PointNet2SASSG.forward) from the levels' int32 FPS indices, one launch."""

@@ -1,0 +1,284 @@
+"""Scene input pipeline: SUN RGB-D infos -> the batch ``DeMFVoteNet.forward_train`` / ``simple_test`` take.
+
+The reference runs mmdet3d 0.18.1 / mmcv pipelines per scene on host workers (configs/demf/demf_votenet.py:184-216)
+[dep-recall: their sources are not in the reference tree]:
+
+    train  LoadPointsFromFile(shift_height, load_dim=6, use_dim=[0,1,2]) -> LoadImageFromFile -> LoadAnnotations3D
+           -> Resize(img_scale, keep_ratio) -> Normalize(to_rgb) -> Pad(32) -> RandomFlip3D(sync_2d=False)
+           -> GlobalRotScaleTrans(rot +-pi/6, scale 0.85-1.15, shift_height) -> PointSample(20000) -> collate
+    test   the same without the 3-D augmentation (MultiScaleFlipAug3D(flip=False)); points are still sampled.
+
+Here the host only reads the ``.bin`` records (``np.fromfile``) and decodes the JPEG (PIL, ``convert('RGB')``, so no
+BGR swap is needed for ``to_rgb``) in a thread pool, draws the per-scene random parameters and packs the batch into
+pinned buffers.  The raw records and uint8 pixels are uploaded as they are and csrc/pipeline.hip does the rest on the
+loader's own stream: the floor percentile, the sample + augmentation, and the resize + normalise + pad.
+
+Random draws: one ``numpy.random.Generator`` per scene draws flip, angle, scale, translation in ``data.augment_3d``'s
+order (``draw_aug_params``), then the 64-bit key of the point sample.  So ``augment_3d(pts, boxes, meta,
+default_rng(s))`` and ``draw_aug_params(default_rng(s))`` apply the same transform; the boxes and metadata are
+produced by replaying those parameters through ``augment_3d`` itself (``apply_aug_params``).  The point sample is a
+keyed permutation, not ``np.random.choice``'s stream: same distribution, different indices.
+"""
+import threading
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import ops
+from .data import augment_3d, resize_meta
+
+ROT_RANGE = (-np.pi / 6, np.pi / 6)            # demf_votenet.py GlobalRotScaleTrans
+SCALE_RANGE = (0.85, 1.15)
+TRANSLATION_STD = (0.0, 0.0, 0.0)
+FLIP_RATIO = 0.5                               # RandomFlip3D flip_ratio_bev_horizontal
+LOAD_DIM = 6
+
+
+def draw_aug_params(rng, flip_ratio=FLIP_RATIO, rot_range=ROT_RANGE, scale_range=SCALE_RANGE,
+                    translation_std=TRANSLATION_STD):
+    """The draws of ``data.augment_3d`` in its order: flip, angle, scale, translation."""
+    flip = bool(rng.random() < flip_ratio)
+    angle = float(rng.uniform(*rot_range))
+    scale = float(rng.uniform(*scale_range))
+    trans = rng.normal(scale=np.asarray(translation_std, np.float64), size=3)
+    return dict(flip=flip, angle=angle, scale=scale, trans=trans)
+
+
+def identity_aug_params():
+    """Test mode: no flip, angle 0, scale 1, no translation."""
+    return dict(flip=False, angle=0.0, scale=1.0, trans=np.zeros(3))
+
+
+class _Replay:
+    """Stands in for the generator ``augment_3d`` draws from and hands back given parameters."""
+
+    def __init__(self, params):
+        self._uniform = iter((params["angle"], params["scale"]))
+        self._trans = np.asarray(params["trans"], np.float64)
+
+    def random(self):
+        return 0.5                              # compared with flip_ratio 1.0 (flip) or 0.0 (no flip)
+
+    def uniform(self, lo, hi):
+        return next(self._uniform)
+
+    def normal(self, scale=None, size=None):
+        return self._trans.copy()
+
+
+def apply_aug_params(boxes, meta, params, sync_2d=False):
+    """Boxes (n,7) and metadata of ``augment_3d`` for given parameters (the points are left to the GPU): the
+    parameters are replayed through ``augment_3d`` itself, so the arithmetic is exactly that function's.
+    -> (boxes fp32, meta with flip / pcd_* / transformation_3d_flow)."""
+    _, bx, m = augment_3d(np.zeros((0, 4), np.float32), np.asarray(boxes, np.float32).reshape(-1, 7), meta,
+                          _Replay(params), flip_ratio=1.0 if params["flip"] else 0.0, sync_2d=sync_2d)
+    return bx, m
+
+
+def param_row(params):
+    """-> the (8,) fp32 row of demf_points_prep: [flip, cos, sin, scale, tx, ty, tz, 0]."""
+    t = np.asarray(params["trans"], np.float64)
+    return np.array([1.0 if params["flip"] else 0.0, np.cos(params["angle"]), np.sin(params["angle"]),
+                     params["scale"], t[0], t[1], t[2], 0.0], np.float32)
+
+
+def pad_to(n, divisor=32):
+    return int(-(-n // divisor) * divisor)
+
+
+def collate_metas(metas, pad_divisor=32):
+    """The collate step's padding: every image is padded to the batch's largest padded shape, which every scene's
+    ``batch_input_shape`` then names (the per-scene padded shape stays in ``pad_shape``).  -> ((Hp, Wp), metas)."""
+    Hp = max(pad_to(m["img_shape"][0], pad_divisor) for m in metas)
+    Wp = max(pad_to(m["img_shape"][1], pad_divisor) for m in metas)
+    out = []
+    for m in metas:
+        m = dict(m)
+        m["batch_input_shape"] = (Hp, Wp)
+        out.append(m)
+    return (Hp, Wp), out
+
+
+class ScenePipeline:
+    """Per-scene host work (``load``) and the batched device work (``to_device``) of one pipeline mode."""
+
+    def __init__(self, dataset, mode="train", img_scale=(1333, 800), num_points=20000, seed=0,
+                 img_norm=ops.IMG_NORM, pad_divisor=32):
+        if mode not in ("train", "test"):
+            raise ValueError(f"mode must be 'train' or 'test', got {mode!r}")
+        self.dataset, self.mode = dataset, mode
+        self.img_scale, self.num_points, self.seed = tuple(img_scale), int(num_points), int(seed)
+        self.img_norm, self.pad_divisor = img_norm, pad_divisor
+
+    def scene_rng(self, index, epoch=0):
+        key = [self.seed, epoch, int(index)] if self.mode == "train" else [self.seed, int(index)]
+        return np.random.default_rng(key)
+
+    def load(self, index, epoch=0):
+        """Host part of one scene: file reads, JPEG decode, random draws, boxes and metadata."""
+        from PIL import Image
+        info = self.dataset.get_data_info(index)
+        raw = np.fromfile(info["pts_filename"], dtype=np.float32)
+        if raw.size == 0 or raw.size % LOAD_DIM:
+            raise ValueError(f"{info['pts_filename']}: {raw.size} floats is not a positive multiple of {LOAD_DIM}")
+        with Image.open(info["img_filename"]) as im:
+            img = np.asarray(im.convert("RGB"), dtype=np.uint8)
+        h, w = img.shape[:2]
+        rng = self.scene_rng(index, epoch)
+        params = draw_aug_params(rng) if self.mode == "train" else identity_aug_params()
+        seed = int(rng.integers(0, 2 ** 63 - 1))
+        meta = dict(sample_idx=info["sample_idx"], pts_filename=info["pts_filename"],
+                    img_filename=info["img_filename"], depth2img=info["depth2img"], flip=False,
+                    img_norm_cfg=dict(mean=np.asarray(self.img_norm[0], np.float32),
+                                      std=np.asarray(self.img_norm[1], np.float32), to_rgb=True))
+        meta = resize_meta(meta, (h, w), self.img_scale, self.pad_divisor)
+        meta["pad_shape"] = tuple(meta["batch_input_shape"]) + (3,)
+        ann = info.get("ann_info")
+        boxes = ann["gt_bboxes_3d"] if ann is not None else np.zeros((0, 7), np.float32)
+        boxes, meta = apply_aug_params(boxes, meta, params)
+        return dict(index=int(index), raw=raw.reshape(-1, LOAD_DIM), img=img, params=params, seed=seed, meta=meta,
+                    gt_bboxes_3d=boxes, gt_labels_3d=None if ann is None else ann["gt_labels_3d"])
+
+    def to_device(self, scenes, device, stream=None):
+        """Pack ``load`` results into pinned buffers, upload them and run the three kernels on ``stream`` (default:
+        the current stream).  -> (batch dict, uploaded bytes).  The batch is valid on ``stream`` once the call
+        returns; another stream must wait on it first."""
+        B = len(scenes)
+        npts = np.array([s["raw"].shape[0] for s in scenes], np.int64)
+        nbytes = np.array([s["img"].size for s in scenes], np.int64)
+        raw_h = torch.empty((int(npts.sum()), LOAD_DIM), dtype=torch.float32, pin_memory=True)
+        img_h = torch.empty((int(nbytes.sum()),), dtype=torch.uint8, pin_memory=True)
+        raw_np, img_np = raw_h.numpy(), img_h.numpy()
+        poff = np.concatenate([[0], np.cumsum(npts)]).astype(np.int64)
+        ioff = np.concatenate([[0], np.cumsum(nbytes)]).astype(np.int64)
+        for b, s in enumerate(scenes):
+            raw_np[poff[b]:poff[b + 1]] = s["raw"]
+            img_np[ioff[b]:ioff[b + 1]] = s["img"].reshape(-1)
+        small = torch.empty((B * 4 + 2 * (B + 1) + B + 2 * B,), dtype=torch.int64, pin_memory=True)
+        sm = small.numpy()
+        sm[:B * 4].view(np.float32)[:] = np.stack([param_row(s["params"]) for s in scenes]).reshape(-1)
+        o = B * 4
+        sm[o:o + B + 1] = poff
+        sm[o + B + 1:o + 2 * B + 2] = ioff
+        sm[o + 2 * B + 2:o + 3 * B + 2] = [s["seed"] for s in scenes]
+        shp = []
+        for s in scenes:
+            h, w = s["img"].shape[:2]
+            nh, nw = s["meta"]["img_shape"][:2]
+            shp += [h, w, nh, nw]
+        sm[o + 3 * B + 2:o + 3 * B + 2 + 2 * B].view(np.int32)[:] = shp
+        (Hp, Wp), metas = collate_metas([s["meta"] for s in scenes], self.pad_divisor)
+        stream = torch.cuda.current_stream(device) if stream is None else stream
+        with torch.cuda.stream(stream):
+            raw_d = raw_h.to(device, non_blocking=True)
+            img_d = img_h.to(device, non_blocking=True)
+            small_d = small.to(device, non_blocking=True)
+            params = small_d[:B * 4].view(torch.float32).view(B, 8)
+            poff_d = small_d[o:o + B + 1]
+            ioff_d = small_d[o + B + 1:o + 2 * B + 2]
+            seeds = small_d[o + 2 * B + 2:o + 3 * B + 2]
+            shapes = small_d[o + 3 * B + 2:o + 3 * B + 2 + 2 * B].view(torch.int32).view(B, 4)
+            floor = ops.points_floor(raw_d, poff_d)
+            points = ops.points_prep(raw_d, poff_d, floor, params, seeds, self.num_points)
+            img = ops.image_prep(img_d, ioff_d, shapes, (Hp, Wp), *self.img_norm)
+            batch = dict(points=points, img=img, img_metas=metas)
+            if all(s["gt_labels_3d"] is not None for s in scenes):
+                batch["gt_bboxes_3d"] = [torch.from_numpy(np.ascontiguousarray(s["gt_bboxes_3d"])).to(device)
+                                         for s in scenes]
+                batch["gt_labels_3d"] = [torch.from_numpy(np.ascontiguousarray(s["gt_labels_3d"])).to(device)
+                                         for s in scenes]
+        uploaded = raw_h.numel() * 4 + img_h.numel() + small.numel() * 8
+        return batch, uploaded
+
+
+class SceneBatch(dict):
+    """A batch dict (``points``, ``img``, ``img_metas`` [, ``gt_bboxes_3d``, ``gt_labels_3d``]) plus ``indices`` (the
+    dataset indices of its scenes) and ``event`` (recorded on the loader's stream behind the batch's kernels)."""
+    indices = ()
+    event = None
+
+    def wait(self, stream=None):
+        """Make ``stream`` (default: the current one) wait for the batch and keep its memory alive there."""
+        stream = torch.cuda.current_stream() if stream is None else stream
+        stream.wait_event(self.event)
+        for v in self.values():
+            for t in (v if isinstance(v, list) else [v]):
+                if isinstance(t, torch.Tensor) and t.is_cuda:
+                    t.record_stream(stream)
+        return self
+
+
+class SceneLoader:
+    """Batches of a dataset through ``ScenePipeline`` with host reads in ``workers`` threads and the device work on
+    the loader's own stream, one batch ahead: while the consumer runs step k, batch k+1's kernels are queued on the
+    loader stream and batch k+2's files are being read.  Every yielded batch has already been made to wait for on
+    the current stream (``SceneBatch.wait``).
+
+    Train mode reshuffles per epoch (a permutation keyed on (seed, epoch)) and draws every scene's augmentation from
+    (seed, epoch, index); iterating the loader again runs the next epoch (RepeatDataset(times=5) is five epochs).
+    Test mode keeps the dataset order, with no augmentation; the point sample is keyed on (seed, index)."""
+
+    def __init__(self, dataset, batch_size, mode="train", seed=0, img_scale=(1333, 800), num_points=20000,
+                 workers=8, drop_last=False, device=None):
+        self.pipeline = ScenePipeline(dataset, mode, img_scale, num_points, seed)
+        self.dataset, self.batch_size, self.mode, self.seed = dataset, int(batch_size), mode, int(seed)
+        self.drop_last = drop_last
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.workers = int(workers)
+        self.epoch = 0
+        self.last_upload_bytes = 0
+        self._stream = None
+        self._lock = threading.Lock()
+
+    def __len__(self):
+        n = len(self.dataset)
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def _order(self, epoch):
+        n = len(self.dataset)
+        if self.mode == "train":
+            return np.random.default_rng([self.seed, epoch]).permutation(n)
+        return np.arange(n)
+
+    def _submit(self, pool, indices, epoch):
+        return [pool.submit(self.pipeline.load, int(i), epoch) for i in indices]
+
+    def _to_device(self, futures, indices):
+        scenes = [f.result() for f in futures]
+        batch, nbytes = self.pipeline.to_device(scenes, self.device, self._stream)
+        self.last_upload_bytes = nbytes
+        out = SceneBatch(batch)
+        out.indices = tuple(int(i) for i in indices)
+        out.event = torch.cuda.Event()
+        out.event.record(self._stream)
+        return out
+
+    def __iter__(self):
+        with self._lock:
+            epoch = self.epoch
+            self.epoch += 1
+        if self._stream is None:
+            self._stream = torch.cuda.Stream(self.device)
+        order = self._order(epoch)
+        bs = self.batch_size
+        chunks = [order[i:i + bs] for i in range(0, len(order), bs)]
+        if self.drop_last and chunks and len(chunks[-1]) < bs:
+            chunks.pop()
+        if not chunks:
+            return
+        pool = ThreadPoolExecutor(max_workers=max(1, self.workers))
+        try:
+            nxt = self._submit(pool, chunks[0], epoch)
+            pending = None
+            for k, idx in enumerate(chunks):
+                cur = nxt
+                if k + 1 < len(chunks):
+                    nxt = self._submit(pool, chunks[k + 1], epoch)
+                ready = self._to_device(cur, idx)
+                if pending is not None:
+                    yield pending.wait()
+                pending = ready
+            yield pending.wait()
+        finally:
+            pool.shutdown(wait=True, cancel_futures=True)

@@ -796,6 +796,38 @@ DEMF_INTERNAL int demf_eval_ap(int C, int T, const int* cls_off, const int* npos
                  const unsigned char* tp_sorted, int* workspace, double* ap, double* rec, demf_stream_t stream);
 
 /* ------------------------------------------------------------------ *
+ * Input pipeline of SUN RGB-D scenes (csrc/pipeline.hip): the per-point and per-pixel steps of the training /
+ * test pipelines of configs/demf/demf_votenet.py:184-216 (mmdet3d 0.18.1 / mmcv transforms).  Scenes are
+ * ragged: `offsets` (B+1) int64 DEVICE arrays into the concatenated raw buffers; `total` / `src_bytes` is the
+ * size of that buffer (points / bytes), and a scene whose offsets fall outside it, or that is empty, yields NaN
+ * (points) or padding (image) instead of a read out of bounds.
+ * ------------------------------------------------------------------ */
+
+/* LoadPointsFromFile(shift_height=True, load_dim=6) (demf_votenet.py:186-190): floor (B) = np.percentile(z, 0.99) of
+ * each scene's whole raw cloud - numpy's linear interpolation between the order statistics of rank
+ * floor(0.0099 (N-1)) and the next - from raw (total, load_dim) float32 records, z in column 2.               */
+DEMF_INTERNAL int demf_points_floor(int B, int load_dim, long long total, const float* raw, const int64_t* offsets,
+                      float* floor_out, demf_stream_t stream);
+
+/* RandomFlip3D + GlobalRotScaleTrans(shift_height=True) + PointSample(num_points) (demf_votenet.py:198-207) on the raw
+ * records: out (B, num_points, 4) = (xyz flipped (x -> -x), rotated by +angle about z, scaled, translated | (z_raw -
+ * floor) * scale).  params (B, 8) fp32 = [flip, cos, sin, scale, tx, ty, tz, unused]; seeds (B) int64.  Source of
+ * point j: with N >= num_points a keyed random permutation of [0, N) (without replacement, random order), else
+ * iid indices (with replacement), as np.random.choice(N, num_points, replace=N < num_points).  src_index
+ * (B, num_points) int32 or NULL.                                                                                  */
+DEMF_INTERNAL int demf_points_prep(int B, int num_points, int load_dim, long long total, const float* raw,
+                     const int64_t* offsets, const float* floor_in, const float* params, const int64_t* seeds,
+                     float* out, int* src_index, demf_stream_t stream);
+
+/* Resize(img_scale, keep_ratio) + Normalize(to_rgb) + Pad(size_divisor=32) + collate padding (demf_votenet.py:192-197):
+ * src = uint8 HWC RGB images at byte offsets, shapes (B, 4) int32 = (h_in, w_in, h_out, w_out) (DEVICE), mean_std =
+ * 6 HOST floats (mean RGB, std RGB) -> out (B, 3, Hp, Wp) fp32, every element written (padding 0).  Bilinear with
+ * cv2 INTER_LINEAR's source coordinates, the resized value rounded to uint8 before normalising.  Wp % 4 == 0.     */
+DEMF_INTERNAL int demf_image_prep(int B, int Hp, int Wp, long long src_bytes, const unsigned char* src,
+                    const int64_t* offsets, const int* shapes, const float* mean_std, float* out,
+                    demf_stream_t stream);
+
+/* ------------------------------------------------------------------ *
  * Optimizer step on flat buffers: torch.optim.AdamW + clip_grad_norm_ as the reference's
  * runner applies them (configs/_base_/schedules/schedule_3x.py:6-7: AdamW lr 0.008, wd 0.01,
  * grad_clip max_norm 10; configs/demf/demf_votenet.py:16-24: 'decoder' lr_mult 0.05).  One call
