@@ -54,6 +54,8 @@ SIGNATURES = {
     "demf_vote_targets": [_c_int] * 4 + [_ptr] * 8,
     "demf_box_extent_count": [_c_int] * 4 + [_ptr] * 8,
     "demf_aligned_nms": [_c_int, _c_int, _c_float] + [_ptr] * 6,
+    "demf_detect_decode": [_c_int] * 6 + [_ptr] * 7 + [_ptr],
+    "demf_detect_pack": [_c_int] * 4 + [_c_float] + [_ptr] * 5 + [_c_int] * 3 + [_ptr] * 5 + [_ptr],
     "demf_box3d_iou": [_c_int, _c_int] + [_ptr] * 4,
     "demf_eval_match": [_c_int, _c_int, _ptr, _c_int, _c_int] + [_ptr] * 7,
     "demf_eval_ap": [_c_int, _c_int] + [_ptr] * 8,
@@ -157,6 +159,14 @@ class DwJob(ctypes.Structure):
     _fields_ = [("R", _c_int), ("N", _c_int), ("K", _c_int), ("ldx", _c_int), ("G", _ptr), ("dP", _ptr), ("arg", _ptr),
                 ("ns", _c_int), ("Y", _ptr), ("vec6", _ptr), ("Xprev", _ptr), ("prev_scale_shift", _ptr), ("dW", _ptr),
                 ("lddw", _c_int)]
+
+
+class DetectLayer(ctypes.Structure):
+    """include/demf_hip.h: demf_detect_layer (field order and types must match)."""
+    _fields_ = [("K", _c_int), ("res_scale", _c_float)] + [
+        f for name in ("center", "center_base", "size", "dir_class", "dir_res", "obj", "sem")
+        for f in ((name, _ptr), ((name if name != "center_base" else "base") + "_sb", _c_int),
+                  ((name if name != "center_base" else "base") + "_sk", _c_int))]
 
 
 class GemmDesc(ctypes.Structure):

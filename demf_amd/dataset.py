@@ -93,7 +93,8 @@ class SUNRGBDDataset:
         return dict(gt_bboxes_3d=boxes, gt_labels_3d=labels)
 
     def evaluate(self, results, metric=(0.25, 0.5), logger=None):
-        """indoor_eval of ``results`` (one ``simple_test`` dict per scene, in dataset order) against the infos'
+        """indoor_eval of ``results`` (one ``simple_test`` dict per scene, in dataset order, or a
+        ``DetectionStore`` holding the scenes in that order) against the infos'
         annotations -> ``{cat}_AP_{t}``, ``mAP_{t}``, ``{cat}_rec_{t}``, ``mAR_{t}`` (evaluation.indoor_eval)."""
         from .evaluation import indoor_eval
         if len(results) != len(self):

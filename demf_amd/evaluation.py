@@ -30,6 +30,7 @@ import torch
 
 from . import ops
 from .config import SUNRGBD_CLASSES
+from .detections import DetectionStore
 
 
 def _rows(x):
@@ -52,7 +53,9 @@ def _offsets(counts):
 
 
 def evaluate_detections(gt_annos, dt_annos, metric=(0.25, 0.5), label2cat=None, with_tp=False, device=None):
-    """The device part of :func:`indoor_eval`.  -> dict(classes = the evaluated labels (ascending),
+    """The device part of :func:`indoor_eval`.  ``dt_annos``: the list of result dicts, or a ``DetectionStore``
+    holding one scene per annotation (its boxes and scores are read on the device, never copied to the host and
+    back; a store whose rows did not fit raises RuntimeError).  -> dict(classes = the evaluated labels (ascending),
     ap / rec = (C, T) float64, and with ``with_tp`` tp = (P, T) uint8 flags of the detections concatenated
     over scenes in scene order)."""
     if len(gt_annos) != len(dt_annos):
@@ -64,19 +67,31 @@ def evaluate_detections(gt_annos, dt_annos, metric=(0.25, 0.5), label2cat=None, 
         label2cat = dict(enumerate(SUNRGBD_CLASSES))
     nscene = len(dt_annos)
 
-    # ---- host: concatenate every scene ----------------------------------------------------------
-    pboxes = [_rows(d["boxes_3d"]).reshape(-1, 7) for d in dt_annos]
-    counts = np.asarray([len(b) for b in pboxes], np.int64)
-    P = int(counts.sum())
-    boxes = np.concatenate(pboxes).astype(np.float32) if P else np.zeros((0, 7), np.float32)
-    scores = np.concatenate([_rows(d["scores_3d"]).reshape(-1) for d in dt_annos]).astype(np.float32) \
-        if nscene else np.zeros(0, np.float32)
-    labels = np.concatenate([_rows(d["labels_3d"]).reshape(-1) for d in dt_annos]).astype(np.int64) \
-        if nscene else np.zeros(0, np.int64)
-    if scores.shape[0] != P or labels.shape[0] != P:
-        raise ValueError("every result needs as many scores_3d and labels_3d as boxes_3d")
-    if np.isnan(scores).any():
-        raise ValueError("detection scores must not be NaN")
+    store = dt_annos if isinstance(dt_annos, DetectionStore) else None
+    if store is not None:
+        # ---- a store: boxes and scores stay where they are; the per-row integers come to the host ---
+        off, P = store.host_index()                                 # (raises if rows did not fit)
+        counts = np.diff(off)
+        pb, sc = store.boxes[:P], store.scores[:P]
+        labels = store.labels[:P].cpu().numpy().astype(np.int64) if P else np.zeros(0, np.int64)
+        if P and bool(torch.isnan(sc).any()):
+            raise ValueError("detection scores must not be NaN")
+        if device is None:
+            device = store.device
+    else:
+        # ---- host: concatenate every scene ------------------------------------------------------
+        pboxes = [_rows(d["boxes_3d"]).reshape(-1, 7) for d in dt_annos]
+        counts = np.asarray([len(b) for b in pboxes], np.int64)
+        P = int(counts.sum())
+        boxes = np.concatenate(pboxes).astype(np.float32) if P else np.zeros((0, 7), np.float32)
+        scores = np.concatenate([_rows(d["scores_3d"]).reshape(-1) for d in dt_annos]).astype(np.float32) \
+            if nscene else np.zeros(0, np.float32)
+        labels = np.concatenate([_rows(d["labels_3d"]).reshape(-1) for d in dt_annos]).astype(np.int64) \
+            if nscene else np.zeros(0, np.int64)
+        if scores.shape[0] != P or labels.shape[0] != P:
+            raise ValueError("every result needs as many scores_3d and labels_3d as boxes_3d")
+        if np.isnan(scores).any():
+            raise ValueError("detection scores must not be NaN")
     scene = np.repeat(np.arange(nscene, dtype=np.int64), counts)
     gb, gl, gs = [], [], []
     for i, a in enumerate(gt_annos):
@@ -121,7 +136,8 @@ def evaluate_detections(gt_annos, dt_annos, metric=(0.25, 0.5), label2cat=None, 
     npos_d, ws_off = up(npos.astype(np.int32)), up(_offsets(npos))
     cls_off = up(_offsets(np.bincount(pcls, minlength=C)))
     if P:
-        pb, sc = up(boxes), up(scores)
+        if store is None:
+            pb, sc = up(boxes), up(scores)
         pseg_d, pcls_d = up(pseg.astype(np.int32)), up(pcls.astype(np.int32))
         skey = _desc_score_key(sc)
         order_seg = torch.sort((pseg_d.to(torch.int64) << 32) | skey, stable=True).indices.to(torch.int32)
@@ -145,7 +161,7 @@ def indoor_eval(gt_annos, dt_annos, metric=(0.25, 0.5), label2cat=None, logger=N
 
     gt_annos: upstream ``info['annos']`` dicts (``gt_num``, ``gt_boxes_upright_depth`` (n,7) gravity-centre,
     ``class`` (n,)); dt_annos: what ``DeMFVoteNet.simple_test`` returns (``boxes_3d`` depth boxes in the
-    bottom-centre form, ``scores_3d``, ``labels_3d``); label2cat: label -> name, default the SUN RGB-D
+    bottom-centre form, ``scores_3d``, ``labels_3d``) or the ``DetectionStore`` that ``predict_into`` filled; label2cat: label -> name, default the SUN RGB-D
     10 classes (config.SUNRGBD_CLASSES).  Boxes are depth boxes (``box_type_3d`` / ``box_mode_3d`` are taken
     for upstream's signature; the depth mode is the only one its indoor datasets use); ``logger`` is
     accepted and no table is printed.

@@ -1,0 +1,97 @@
+"""The test loop and its command line: what the reference's ``eval.py --eval mAP`` does (README.md:43-46).
+
+  python -m demf_amd.infer --data-root R --ann-file sunrgbd_infos_val.pkl --checkpoint C
+                           [--batch-size 8] [--workers 8] [--out results.pkl] [--no-eval]
+
+``run_test`` feeds a dataset through ``SceneLoader(mode="test")`` and ``DeMFVoteNet.predict_into``; the
+detections of every scene stay on the device in one ``DetectionStore`` and nothing in the loop waits for the
+GPU, so the loader's one-batch-ahead overlap holds.  Single process, one GPU.
+"""
+import argparse
+import json
+import pickle
+import sys
+
+import torch
+
+from .detections import DetectionStore
+from .pipeline import SceneLoader
+
+
+def run_test(model, dataset, batch_size=8, workers=8, num_points=20000, img_scale=(1333, 800), seed=0,
+             store=None):
+    """Detections of every scene of ``dataset`` in dataset order -> the ``DetectionStore`` holding them (``store``,
+    or a new worst-case one).  The last batch may be smaller; there is no host sync inside the loop."""
+    loader = SceneLoader(dataset, batch_size, "test", seed=seed, img_scale=img_scale, num_points=num_points,
+                         workers=workers)
+    model.eval()
+    if store is None:
+        store = DetectionStore(max(len(dataset), 1), device=loader.device)
+    for batch in loader:
+        model.predict_into(store, **batch)
+    return store
+
+
+def _model_state(ckpt):
+    """The model's state dict inside an mmcv checkpoint ({"state_dict": ...}, what the reference publishes), a
+    ``Trainer.state_dict()`` ({"model": ...}) or a bare state dict."""
+    if not isinstance(ckpt, dict):
+        raise ValueError(f"a checkpoint is a dict, got {type(ckpt).__name__}")
+    for key in ("state_dict", "model"):
+        if isinstance(ckpt.get(key), dict):
+            return ckpt[key]
+    if ckpt and all(isinstance(v, torch.Tensor) for v in ckpt.values()):
+        return ckpt
+    raise ValueError("checkpoint layout not recognised: expected {'state_dict': ...}, {'model': ...} or a state dict")
+
+
+def load_checkpoint(model, path):
+    """Load the weights at ``path`` into ``model`` through its ``load_state_dict`` (for ``DeMFVoteNet`` that
+    applies the stage-1 key remap).  Missing or unexpected keys are an error."""
+    ckpt = torch.load(path, map_location="cpu", weights_only=True)
+    model.load_state_dict(_model_state(ckpt), strict=True)
+    return model
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(prog="python -m demf_amd.infer", description=__doc__.split("\n")[0])
+    p.add_argument("--data-root", required=True)
+    p.add_argument("--ann-file", required=True, help="infos file, absolute or relative to --data-root")
+    p.add_argument("--checkpoint", required=True)
+    p.add_argument("--batch-size", type=int, default=8)
+    p.add_argument("--workers", type=int, default=8)
+    p.add_argument("--out", default=None, help="pickle the per-scene results (the reference's --out)")
+    p.add_argument("--no-eval", action="store_true", help="do not evaluate (then --out is required)")
+    args = p.parse_args(argv)
+    if args.batch_size < 1 or args.workers < 1:
+        p.error("--batch-size and --workers must be positive")
+    if args.no_eval and not args.out:
+        p.error("--no-eval without --out would discard the detections")
+    return args
+
+
+def main(argv=None, model=None, **loader_kwargs):
+    """-> the ``indoor_eval`` dict (None with ``--no-eval``), also printed as one JSON line.  ``model``: the
+    detector to use instead of the full-size ``DeMFVoteNet()``; ``loader_kwargs`` go to ``run_test``
+    (``num_points``, ``img_scale``, ``seed``)."""
+    args = parse_args(argv)
+    from .dataset import SUNRGBDDataset
+    dataset = SUNRGBDDataset(args.data_root, args.ann_file, test_mode=True)
+    if model is None:
+        from .modules import DeMFVoteNet
+        model = DeMFVoteNet()
+    load_checkpoint(model, args.checkpoint)
+    model.cuda()
+    store = run_test(model, dataset, batch_size=args.batch_size, workers=args.workers, **loader_kwargs)
+    if args.out:
+        with open(args.out, "wb") as f:
+            pickle.dump(store.results(), f)
+    if args.no_eval:
+        return None
+    ret = dataset.evaluate(store)
+    print(json.dumps(ret))
+    return ret
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

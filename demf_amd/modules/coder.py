@@ -17,6 +17,7 @@ class _Preds(dict):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self.lazy = {}                 # key -> zero-argument callable
+        self.recipe = {}               # key -> the recipe's operands, for consumers that fuse it (ops.detect_decode)
 
     def _lazy(self, only=None):
         for key in ([only] if only is not None else list(self.lazy)):
@@ -61,6 +62,7 @@ class _Preds(dict):
     def copy(self):
         out = _Preds(dict.items(self))
         out.lazy = dict(self.lazy)
+        out.recipe = dict(self.recipe)
         return out
 
 
@@ -128,12 +130,14 @@ class DeMFClassAgnosticBBoxCoder:
         # raw conv rows - same values, no copy kernels; consumers that need dense memory copy)
         # "center" = base_xyz + reg[..., 0:3]: materialised on first access (see _Preds)
         results.lazy["center"] = lambda: base_xyz + reg_t[..., 0:3]
+        results.recipe["center"] = (base_xyz, reg_t[..., 0:3])
         results["size"] = reg_t[..., 3:6]
         results["dir_class"] = reg_t[..., 6:6 + nb]
         dir_res_norm = reg_t[..., 6 + nb:6 + 2 * nb]
         results["dir_res_norm"] = dir_res_norm
         # "dir_res" = dir_res_norm * (pi / nb) is only read by decode(): materialised on first access
         results.lazy["dir_res"] = lambda: dir_res_norm * (np.pi / nb)
+        results.recipe["dir_res"] = (dir_res_norm, np.pi / nb)
         results["obj_scores"] = cls_t[..., 0:2]
         if with_sem:
             results["sem_scores"] = cls_t[..., 2:]

@@ -87,6 +87,7 @@ class DeMFVoteNet(DeMFHotPath):
 
       forward_train(points, img, img_metas, gt_bboxes_3d, gt_labels_3d) -> dict of losses  (:134-170)
       simple_test(points, img_metas, img) -> list of dict(boxes_3d, scores_3d, labels_3d)  (:254-283)
+      predict_into(store, points, img_metas, img): the same detections appended to a device-resident store
       forward_test(points, img_metas, img)  (single-augmentation form of :172-238)
     """
 
@@ -133,8 +134,18 @@ class DeMFVoteNet(DeMFHotPath):
         if isinstance(points, (list, tuple)):
             points = torch.stack(points)                                    # :262
         bbox_preds = self.forward_head(points, img_features, img_metas)    # :263-275
-        bbox_list = self.pts_bbox_head.get_bboxes(points, bbox_preds, img_metas, rescale=rescale)
-        return [bbox3d2result(b, s, l) for b, s, l in bbox_list]           # :278-282
+        # :278-282 (get_bboxes + bbox3d2result): the batch's store, brought to the host in one go
+        return self.pts_bbox_head.get_bboxes_packed(points, bbox_preds, img_metas).results()
+
+    @torch.no_grad()
+    def predict_into(self, store, points=None, img_metas=None, img=None, **unused):
+        """``simple_test`` whose detections stay on the device: the batch's scenes are appended to ``store``
+        (detections.DetectionStore) and nothing is returned; the post-processing does not synchronise."""
+        img_features = self.extract_img_feat(img, img_metas)
+        if isinstance(points, (list, tuple)):
+            points = torch.stack(points)
+        bbox_preds = self.forward_head(points, img_features, img_metas)
+        self.pts_bbox_head.get_bboxes_packed(points, bbox_preds, img_metas, store)
 
     def forward_test(self, points=None, img_metas=None, img=None, bboxes_2d=None, **kwargs):
         """:172-238 for one augmentation (the only form the reference implements for points +

@@ -571,44 +571,70 @@ class DeMFVoteHead(nn.Module):
         return seven, vote
 
     # ---- test-time decode + NMS: :714-754 --------------------------------------------
+    def _decode_layers(self, bbox_preds):
+        """The ensemble layers of ``test_cfg`` in the form ops.detect_decode reads: the views of the raw conv
+        rows as they are; ``center`` / ``dir_res`` that split_pred has not materialised go in as their recipes
+        (base_xyz + reg[..., 0:3], dir_res_norm * (pi / nb)) and are computed in the kernel."""
+        layers = []
+        for i in self.test_cfg["ensemble_layers"]:
+            d = bbox_preds["decode_res_all"][i]
+            recipe = getattr(d, "recipe", {})
+            y = dict(size=d["size"], dir_class=d["dir_class"], obj=d["obj_scores"], sem=d["sem_scores"])
+            if "center" in recipe and not dict.__contains__(d, "center"):
+                y["center_base"], y["center"] = recipe["center"]
+            else:
+                y["center"] = d["center"]
+            if "dir_res" in recipe and not dict.__contains__(d, "dir_res"):
+                y["dir_res"], y["res_scale"] = recipe["dir_res"]
+            else:
+                y["dir_res"] = d["dir_res"]
+            layers.append(y)
+        return layers
+
+    @torch.no_grad()
+    def get_bboxes_packed(self, points, bbox_preds, input_metas, store=None):
+        """``get_bboxes`` into a ``DetectionStore`` (a fresh worst-case one for the batch when none is given):
+        decode + score -> extent / point count -> class-aware aligned NMS -> pack, four kernels of
+        csrc/detect.hip and csrc/postprocess.hip around one ``count > 5`` mask.  No launch has a shape that
+        depends on data and nothing synchronises with the host; the batch's scenes are appended to ``store`` in
+        order, rows in the reference's order.  -> the store."""
+        from ..detections import DetectionStore
+        tc = self.test_cfg
+        box7, cosy, siny, obj, sem, classes = ops.detect_decode(
+            self._decode_layers(bbox_preds), self.num_dir_bins, self.bbox_coder.with_rot)
+        if isinstance(points, (list, tuple)):
+            points = torch.stack(points)
+        bottom, extent, count = ops.box_extent_count(points.contiguous(), box7, (cosy, siny))
+        keep = ops.aligned_nms(extent, obj, classes, count > 5, tc["nms_thr"], as_bytes=True)
+        B, K, C = sem.shape
+        per_class = bool(tc["per_class_proposal"])
+        if store is None:
+            store = DetectionStore(max(B, 1), device=sem.device)
+        first = store.reserve(B, K * (C if per_class else 1))
+        ops.detect_pack(keep, obj, sem, classes, bottom, tc["score_thr"], per_class, first, store.boxes,
+                        store.scores, store.labels, store.scene_off, store.state)
+        return store
+
     @torch.no_grad()
     def get_bboxes(self, points, bbox_preds, input_metas, rescale=False, use_nms=True):
         """Same contract as the reference: the decode results of ``test_cfg.ensemble_layers`` are
         concatenated, boxes holding <= 5 points are dropped, class-aware aligned NMS
         (csrc/postprocess.hip) and the score threshold select the survivors, and every survivor is
         reported once per class (``per_class_proposal``).  -> list of (boxes, scores, labels) per
-        scene, or the raw (B,K,7) boxes when ``use_nms`` is False."""
-        decode_res_all = bbox_preds["decode_res_all"]
-        tc = self.test_cfg
-        obj, sem, box = [], [], []
-        for i in tc["ensemble_layers"]:
-            d = decode_res_all[i]
-            obj.append(F.softmax(d["obj_scores"], dim=-1)[..., -1])
-            sem.append(F.softmax(d["sem_scores"], dim=-1))
-            box.append(self.bbox_coder.decode(d))
-        obj, sem = torch.cat(obj, 1).contiguous(), torch.cat(sem, 1)
-        box = torch.cat(box, 1).contiguous()
+        scene, or the raw (B,K,7) boxes when ``use_nms`` is False.  With NMS this is the unpacking of
+        ``get_bboxes_packed``: one host sync per call, the results stay on the device."""
         if not use_nms:
-            return box
-        if isinstance(points, (list, tuple)):
-            points = torch.stack(points)
-        bottom, extent, count = ops.box_extent_count(points.contiguous(), box)
-        classes = torch.argmax(sem, -1)
-        keep = ops.aligned_nms(extent, obj, classes, count > 5, tc["nms_thr"])
-        selected = keep & (obj > tc["score_thr"])
+            return ops.detect_decode(self._decode_layers(bbox_preds), self.num_dir_bins,
+                                     self.bbox_coder.with_rot)[0]
+        store = self.get_bboxes_packed(points, bbox_preds, input_metas)
+        off, rows = store.host_index()
+        labels = store.labels[:rows].to(torch.int64)
         results = []
-        for b in range(box.shape[0]):
-            sel = selected[b]
-            bx, sc, cl = bottom[b][sel], obj[b][sel], classes[b][sel]
-            if tc["per_class_proposal"]:
-                C = sem.shape[-1]
-                ss = sem[b][sel]                                           # (n, C)
-                bx = bx.repeat(C, 1)
-                sc = (sc[None, :] * ss.t()).reshape(-1)
-                cl = torch.arange(C, device=cl.device, dtype=cl.dtype).repeat_interleave(int(sel.sum()))
+        for b, (lo, hi) in enumerate(zip(off[:-1].tolist(), off[1:].tolist())):
+            bx = store.boxes[lo:hi]
             wrap = input_metas[b].get("box_type_3d") if input_metas is not None else None
             results.append((wrap(bx, box_dim=bx.shape[-1], with_yaw=self.bbox_coder.with_rot)
-                            if wrap is not None else DepthBoxes(bx), sc, cl))
+                            if wrap is not None else DepthBoxes(bx), store.scores[lo:hi], labels[lo:hi]))
         return results
 
     # ---- targets: :756-941, batched ----------------------------------------------

@@ -1934,15 +1934,19 @@ def proposal_targets(agg, gt, lab, valid, dir_class, dir_res, with_rot, pos_thr,
     return out
 
 
-def box_extent_count(points, boxes7):
+def box_extent_count(points, boxes7, cos_sin=None):
     """points (B,N,>=3), boxes7 (B,K,7) gravity-centre boxes -> (boxes_bottom (B,K,7),
-    extent (B,K,6), count (B,K) int32): see demf_box_extent_count."""
+    extent (B,K,6), count (B,K) int32): see demf_box_extent_count.  cos_sin: (cos, sin) of the yaw, each (B,K),
+    when the caller has them already (detect_decode)."""
     _chk(points, "points")
     _chk(boxes7, "boxes7")
     B, N, stride = points.shape
     K = boxes7.shape[1]
-    yaw = boxes7[..., 6]
-    c, s = torch.cos(yaw).contiguous(), torch.sin(yaw).contiguous()
+    if cos_sin is not None:
+        c, s = _chk(cos_sin[0], "cos"), _chk(cos_sin[1], "sin")
+    else:
+        yaw = boxes7[..., 6]
+        c, s = torch.cos(yaw).contiguous(), torch.sin(yaw).contiguous()
     out = torch.empty_like(boxes7)
     ext = torch.empty((B, K, 6), dtype=torch.float32, device=points.device)
     cnt = torch.empty((B, K), dtype=torch.int32, device=points.device)
@@ -1951,16 +1955,87 @@ def box_extent_count(points, boxes7):
     return out, ext, cnt
 
 
-def aligned_nms(extent, scores, classes, valid, iou_thr):
-    """Class-aware greedy NMS on axis-aligned extents (B,K,6) per scene -> keep (B,K) bool."""
+def aligned_nms(extent, scores, classes, valid, iou_thr, as_bytes=False):
+    """Class-aware greedy NMS on axis-aligned extents (B,K,6) per scene -> keep (B,K) bool (``as_bytes``: the
+    uint8 array the kernel wrote, without the conversion launch)."""
     _chk(extent, "extent")
     _chk(scores, "scores")
     _chk(classes, "classes", torch.int64)
     B, K = scores.shape
     keep = torch.empty((B, K), dtype=torch.uint8, device=scores.device)
+    # a bool mask is one byte of 0 / 1 per box: read where it lies
+    valid = valid.contiguous().view(torch.uint8) if valid.dtype == torch.bool else valid.to(torch.uint8).contiguous()
     _ffi.call("demf_aligned_nms", B, K, float(iou_thr), _p(extent), _p(scores), _p(classes),
-              _p(valid.to(torch.uint8).contiguous()), _p(keep), _stream())
-    return keep.bool()
+              _p(valid), _p(keep), _stream())
+    return keep if as_bytes else keep.bool()
+
+
+DETECT_MAX_LAYERS = 8
+_DETECT_FIELDS = (("center", "center", 3), ("center_base", "base", 3), ("size", "size", 3),
+                  ("dir_class", "dir_class", None), ("dir_res", "dir_res", None), ("obj", "obj", 2),
+                  ("sem", "sem", None))
+
+
+def detect_decode(layers, num_dir_bins, with_rot=True):
+    """Decode + score of ``DeMFVoteHead.get_bboxes`` for every ensemble layer in one launch (see
+    demf_detect_decode).  layers: dicts of (B, K_l, n) fp32 arrays ``center`` [+ ``center_base``: their sum is the
+    centre], ``size``, ``dir_class``, ``dir_res`` [* ``res_scale``], ``obj`` (logits), ``sem`` (logits); any view
+    with a unit last stride goes in by pointer and strides, without a copy.
+    -> box7 (B,K,7), cos_yaw, sin_yaw, obj (B,K), sem (B,K,C), classes (B,K) int64 with K = sum K_l."""
+    if not 1 <= len(layers) <= DETECT_MAX_LAYERS:
+        raise ValueError(f"detect_decode takes 1 to {DETECT_MAX_LAYERS} layers, got {len(layers)}")
+    B, _, C = layers[0]["sem"].shape
+    descs = (_ffi.DetectLayer * len(layers))()
+    hold = []                                       # keeps the (rare) dense copies alive until the launch
+    for d, y in zip(descs, layers):
+        d.K = y["sem"].shape[1]
+        d.res_scale = float(y.get("res_scale", 1.0))
+        for key, name, n in _DETECT_FIELDS:
+            t = y.get(key)
+            if t is None:
+                if key in ("center_base",) or (not with_rot and key in ("dir_class", "dir_res")):
+                    continue
+                raise ValueError(f"detect_decode: a layer has no {key!r}")
+            n = n if n is not None else (C if key == "sem" else num_dir_bins)
+            if not t.is_cuda or t.dtype != torch.float32:
+                raise RuntimeError(f"{key} must be a float32 GPU (HIP) tensor: demf_amd operators have no CPU path")
+            if tuple(t.shape) != (B, d.K, n):
+                raise ValueError(f"{key} must be {(B, d.K, n)}, got {tuple(t.shape)}")
+            if t.stride(-1) != 1 or max(t.stride(0), t.stride(1)) >= (1 << 31):
+                t = t.contiguous()
+                hold.append(t)
+            setattr(d, key, t.data_ptr())
+            setattr(d, name + "_sb", t.stride(0))
+            setattr(d, name + "_sk", t.stride(1))
+    K = sum(d.K for d in descs)
+    dev = layers[0]["sem"].device
+    f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)         # noqa: E731
+    box7, cosy, siny, obj, sem = f(B, K, 7), f(B, K), f(B, K), f(B, K), f(B, K, C)
+    cls = torch.empty((B, K), dtype=torch.int64, device=dev)
+    _ffi.call("demf_detect_decode", B, K, len(layers), C, int(num_dir_bins), int(bool(with_rot)), descs,
+              _p(box7), _p(cosy), _p(siny), _p(obj), _p(sem), _p(cls), _stream())
+    return box7, cosy, siny, obj, sem, cls
+
+
+def detect_pack(keep, obj, sem, classes, boxes_bottom, score_thr, per_class, first_scene, boxes, scores, labels,
+                scene_off, state):
+    """Append a batch's survivors (keep & obj > score_thr) to the arrays of a ``DetectionStore`` in the
+    reference's row order (see demf_detect_pack).  Nothing is returned and nothing is synchronised: the row
+    counts stay on the device (scene_off, state)."""
+    _chk(keep, "keep", torch.uint8)
+    _chk(obj, "obj")
+    _chk(sem, "sem")
+    _chk(classes, "classes", torch.int64)
+    _chk(boxes_bottom, "boxes_bottom")
+    _chk(boxes, "boxes")
+    _chk(scores, "scores")
+    _chk(labels, "labels", torch.int32)
+    _chk(scene_off, "scene_off", torch.int32)
+    _chk(state, "state", torch.int32)
+    B, K, C = sem.shape
+    _ffi.call("demf_detect_pack", B, K, C, int(bool(per_class)), float(score_thr), _p(keep), _p(obj), _p(sem),
+              _p(classes), _p(boxes_bottom), int(first_scene), scene_off.numel() - 1, scores.numel(), _p(boxes),
+              _p(scores), _p(labels), _p(scene_off), _p(state), _stream())
 
 
 # --------------------------------------------------------------------------

@@ -767,6 +767,44 @@ DEMF_INTERNAL int demf_aligned_nms(int B, int K, float iou_thr, const float* ext
                      const int64_t* classes, const unsigned char* valid, unsigned char* keep,
                      demf_stream_t stream);
 
+/* One ensemble layer of DeMFVoteHead.get_bboxes (class_agnostic_vote_head.py:714-754) as the decode reads it:
+ * every field is a (B, K, n) array with a unit last stride, given by pointer, batch stride (_sb) and row
+ * stride (_sk) in floats - the views of the raw conv-head rows go in as they are.  center_base != NULL:
+ * center = center_base + center (class_agnostic_bbox_coder.py:214, base_xyz + reg[..., 0:3]);
+ * dir_res is multiplied by res_scale (1, or pi / num_dir_bins for dir_res_norm, :233).                     */
+typedef struct demf_detect_layer {
+  int K;
+  float res_scale;
+  const float* center; int center_sb, center_sk;
+  const float* center_base; int base_sb, base_sk;
+  const float* size; int size_sb, size_sk;
+  const float* dir_class; int dir_class_sb, dir_class_sk;
+  const float* dir_res; int dir_res_sb, dir_res_sk;
+  const float* obj; int obj_sb, obj_sk;
+  const float* sem; int sem_sb, sem_sk;
+} demf_detect_layer;
+
+/* Decode + score of get_bboxes (class_agnostic_vote_head.py:714-733) for L <= 8 ensemble layers (HOST array)
+ * in one launch, in the concatenated (B, K = sum K_l) layout: box7 (B,K,7) = the coder's decode (gravity
+ * centre, size, yaw in [0, 2pi)), cos_yaw / sin_yaw (B,K), obj (B,K) = softmax(obj_scores)[..., 1],
+ * sem (B,K,C) = softmax(sem_scores), classes (B,K) = argmax(sem).  K > 1024 returns DEMF_EUNSUPPORTED.   */
+DEMF_INTERNAL int demf_detect_decode(int B, int K, int L, int C, int num_dir_bins, int with_rot,
+                       const demf_detect_layer* layers, float* box7, float* cos_yaw, float* sin_yaw,
+                       float* obj, float* sem, int64_t* classes, demf_stream_t stream);
+
+/* Selection of get_bboxes (class_agnostic_vote_head.py:735-754; mmdet3d multiclass_nms_single's
+ * per_class_proposal branch) into a detection store: survivors = keep & (obj > score_thr).  Scene b of the batch
+ * becomes store scene first_scene + b; its rows start at scene_off[first_scene] + the rows of the batch's
+ * earlier scenes and are class-major, proposal index ascending inside a class, score = obj * sem[c], label = c
+ * (per_class = 0: one row per survivor, score = obj, label = classes).  Writes scene_off[first_scene + 1 ..
+ * first_scene + B], state[0] = scene_off[first_scene + B] (rows needed so far) and, if a row index reaches
+ * max_rows, state[1] = 1; such rows are counted but not written.  boxes (max_rows,7) bottom-centre, scores
+ * (max_rows), labels (max_rows) int32, scene_off (max_scenes + 1).  K > 1024 returns DEMF_EUNSUPPORTED.  */
+DEMF_INTERNAL int demf_detect_pack(int B, int K, int C, int per_class, float score_thr,
+                     const unsigned char* keep, const float* obj, const float* sem, const int64_t* classes,
+                     const float* boxes_bottom, int first_scene, int max_scenes, int max_rows, float* boxes,
+                     float* scores, int* labels, int* scene_off, int* state, demf_stream_t stream);
+
 /* ------------------------------------------------------------------ *
  * Indoor detection evaluation (csrc/eval3d.hip): mmdet3d 0.18.1 indoor_eval as SUNRGBDDataset.evaluate
  * calls it for `eval.py --eval mAP` (configs/_base_/datasets/sunrgbd-3d-10class.py:107).
