@@ -265,16 +265,20 @@ class FlatAdamW:
         self.t = int(sd["t"])
         self.set_lr_factor(float(sd.get("lr_factor", 1.0)))
 
-    def step(self, max_norm=0.0, grad_scale=1.0, norm_taken=False):
+    def step(self, max_norm=0.0, grad_scale=1.0, norm_taken=False, meter=None, scalars=None):
         """One update of every group from the flat gradient buffer.  ``norm_taken``: the squared norm
         of the gradients is already in the device state (the captured pack took it,
-        demf_multi_copy_sumsq); otherwise one reduction launch over the flat buffer comes first."""
+        demf_multi_copy_sumsq); otherwise one reduction launch over the flat buffer comes first.
+        ``meter`` (meter.StepMeter) with the step's loss ``scalars``: one more launch, between the point
+        where the norm is complete in the state and the AdamW launch that clears it."""
         import ctypes
         from . import _ffi
         self.check_aliasing()
         stream = torch.cuda.current_stream().cuda_stream
         if max_norm > 0.0 and not norm_taken:
             _ffi.call("demf_sumsq_f32", self.grads.numel(), self.grads.data_ptr(), self.state.data_ptr(), stream)
+        if meter is not None:
+            meter.record(scalars, self.state, grad_scale, max_norm)
         a = [ctypes.cast(x, ctypes.c_void_p) for x in self._seg]
         _ffi.call("demf_adamw_state_f32", len(self.segments), a[0], a[1], a[2], a[3], self.flat.data_ptr(),
                   self.grads.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
@@ -302,8 +306,14 @@ def _gc_paused():
 class Trainer:
     """fwd -> loss -> bwd -> one all-reduce -> clip -> AdamW, as one callable step."""
 
-    def __init__(self, model, lr=0.008, weight_decay=0.01, max_grad_norm=10.0):
+    def __init__(self, model, lr=0.008, weight_decay=0.01, max_grad_norm=10.0, forward=None):
+        """``forward``: called instead of ``model.forward_train`` with the same arguments (a detector whose own
+        ``forward_train`` takes the image runs its hot path through this: demf_amd/train.py)."""
         self.model = model
+        self._forward = forward
+        self.meter = None
+        self._loss_scalars = None          # with a meter: the loss dict's device scalars of the last forward
+        self._pending_scalars = None       # ... of the step whose deferred update is still owed
         groups = model.param_groups(lr=lr, weight_decay=weight_decay)
         self.flat = FlatGrads([p for g in groups for p in g["params"]])
         self.max_grad_norm = max_grad_norm
@@ -322,6 +332,21 @@ class Trainer:
         self.opt = FlatAdamW(groups, self.flat) if self.fused else \
             torch.optim.AdamW(groups, lr=lr, weight_decay=weight_decay, foreach=True)
         self._base_lrs = [float(g["lr"]) for g in groups]
+
+    def attach_meter(self, meter):
+        """Meter every optimizer step from now on (meter.StepMeter over ``meter.loss_names()``): one
+        ``demf_step_meter`` launch per step in front of the AdamW launch - in the stream of an eager update, as a
+        node of a step captured with its update.  Attach BEFORE capturing: a captured step is metered or not for
+        good, and its replay refuses to run if that no longer matches the trainer.  Without a meter nothing
+        changes.  ``None`` detaches."""
+        if meter is not None and not self.fused:
+            raise RuntimeError("attach_meter: the step meter is a device kernel; this trainer runs the CPU / gloo "
+                               "path (torch.optim.AdamW), which has nothing to meter")
+        if meter is not None:
+            self.flush()
+            meter.next_t = self.opt.t
+        self.meter = meter
+        self._loss_scalars = self._pending_scalars = None
 
     def set_epoch(self, epoch, steps=(24, 32), gamma=0.1):
         """The reference's step schedule (configs/_base_/schedules/schedule_3x.py:7-9:
@@ -361,9 +386,15 @@ class Trainer:
         kw = {} if geometry is None else dict(geometry=geometry)
         # (the fused decoder layer advances its counter-based dropout state by itself, inside the
         # forward and therefore inside the captured graph: demf_amd/fused.py)
-        losses = self.model.forward_train(batch["points"], batch["img_features"],
-                                          batch["img_metas"], batch["gt_bboxes_3d"],
-                                          batch["gt_labels_3d"], **kw)
+        fwd = self.model.forward_train if self._forward is None else self._forward
+        losses = fwd(batch["points"], batch["img_features"], batch["img_metas"], batch["gt_bboxes_3d"],
+                     batch["gt_labels_3d"], **kw)
+        if self.meter is not None:
+            missing = [k for k in self.meter.names if k not in losses]
+            if missing:
+                raise RuntimeError("the step meter expects the loss terms %s; this forward did not produce %s (the "
+                                   "fused loss path hands out all of them)" % (list(self.meter.names), missing))
+            self._loss_scalars = [losses[k].detach() for k in self.meter.names]
         # the head hands out the sum of its losses directly (one node instead of 8 selects)
         return losses["_total"] if "_total" in losses else torch.stack(list(losses.values())).sum()
 
@@ -433,10 +464,16 @@ class Trainer:
             e1.record()
             ev.append((e0, e1))
 
-    def _finish_update(self, norm_taken=False):
+    def _finish_update(self, norm_taken=False, scalars=None):
         world = dist.get_world_size() if dist.is_initialized() else 1
         # (the norm is that of the SUM over ranks; 1/world is applied in-kernel)
-        self.opt.step(self.max_grad_norm, 1.0 / world, norm_taken=norm_taken)
+        if self.meter is None:
+            self.opt.step(self.max_grad_norm, 1.0 / world, norm_taken=norm_taken)
+            return
+        # metered: ``scalars`` are the loss tensors of the step this update belongs to - a captured step's own
+        # (its replay closure owns them), else those of the last forward
+        self.opt.step(self.max_grad_norm, 1.0 / world, norm_taken=norm_taken, meter=self.meter,
+                      scalars=self._loss_scalars if scalars is None else scalars)
 
     def _captured_update(self, world):
         """The update as nodes of the step's graph (called while capturing, behind the gradient pack).  One
@@ -453,9 +490,10 @@ class Trainer:
         if getattr(self, "_pending_update", False):
             self._pending_update = False
             torch.cuda.current_stream().wait_stream(self._comm())
-            self._finish_update()
+            scalars, self._pending_scalars = self._pending_scalars, None
+            self._finish_update(scalars=scalars)
 
-    def _update(self, defer=False):
+    def _update(self, defer=False, scalars=None):
         if self.fused:
             self.flush()
             world, stub, overlap = self.allreduce_config()
@@ -465,10 +503,12 @@ class Trainer:
                 with torch.cuda.stream(comm):
                     self._collective(world, stub)
                 self._pending_update = True
+                if self.meter is not None:
+                    self._pending_scalars = self._loss_scalars if scalars is None else scalars
                 return
             if world > 1 or stub > 0:
                 self._collective(world, stub)
-            self._finish_update()
+            self._finish_update(scalars=scalars)
             return
         self.flat.all_reduce_mean()
         self.flat.clip_(self.max_grad_norm)
@@ -678,6 +718,11 @@ class Trainer:
         if restore is not None:
             restore()
             torch.cuda.synchronize()
+        # A metered step: the loss tensors the meter launch reads live in THIS graph's pool and belong to this
+        # replay closure (StepCache keeps several graphs alive; the trainer's own reference moves on with every
+        # forward).  In the graph, the captured launch holds their addresses; outside, the eager update gets them.
+        metered = self.meter is not None
+        scalars = self._loss_scalars if metered else None
         one_deep = not os.environ.get("DEMF_GEO_TWO_DEEP")         # A/B: see replay()
 
         def replay(next_points=None):
@@ -694,13 +739,17 @@ class Trainer:
             same version) and otherwise recomputes it.  ``next_points=None`` recomputes the
             pre-pass of the cloud last given (every step still pays for one full pre-pass)."""
             main = torch.cuda.current_stream()
+            if (self.meter is not None) != metered:
+                raise RuntimeError("this step was captured %s a step meter and the trainer now has %s: capture again"
+                                   % (("with", "none") if metered else ("without", "one")))
             if update_in_graph:
                 w_now, stub_now, _ = self.allreduce_config()
                 if w_now != world_c or stub_now:
                     raise RuntimeError("this step was captured with its optimizer update inside the graph "
                                        "(world %d, no all-reduce stub); capture again with update_in_graph=False"
                                        % world_c)
-            update = (lambda defer=False: None) if update_in_graph else self._update
+            update = (lambda defer=False: None) if update_in_graph else self._update if not metered else \
+                (lambda defer=False: self._update(defer, scalars=scalars))
             if can_prefetch and os.environ.get("DEMF_SKIP_GEO"):     # measurement only: the step alone
                 self.flush()
                 graph.replay()
@@ -789,6 +838,7 @@ class Trainer:
 
         replay.load = load
         replay.update_in_graph = update_in_graph
+        replay.metered = metered
         replay.static = static
         replay.geo = geo
         replay.max_gt = G

@@ -2267,3 +2267,30 @@ def msda_sample_then_project(tokens, keep4, spatial_shapes, level_start_index, s
         (ksum.view(B * Q, H).t().unsqueeze(-1) * bias.view(H, 1, Dh)),
         zh, weight.view(H, Dh, C).transpose(1, 2))
     return out.transpose(0, 1).reshape(B, Q, H * Dh)
+
+
+# --------------------------------------------------------------------------
+# Step meter (csrc/meter.hip)
+# --------------------------------------------------------------------------
+METER_ROW_WORDS, METER_HEAD_WORDS, METER_MAX_SCALARS = 16, 6, 10      # include/demf_hip.h: DEMF_METER_*
+METER_FLAG_GRAD_NORM = 1 << 16
+
+
+def step_meter(scalars, opt_state, grad_scale, max_norm, ring):
+    """One record of the step in flight into ``ring`` ((rows, 16) int32, row ``t % rows``): the stamp ``t`` and
+    ``lr_factor`` of ``opt_state`` (FlatAdamW.state), the pre-clip gradient norm and clip coefficient its squared
+    norm gives, and ``scalars`` - up to 10 single-element fp32 device tensors, views at any offset.  Launch it
+    after the norm is complete and before the AdamW launch that clears it; row layout in include/demf_hip.h."""
+    if not 1 <= len(scalars) <= METER_MAX_SCALARS:
+        raise ValueError("step_meter takes 1..%d scalars, got %d" % (METER_MAX_SCALARS, len(scalars)))
+    for s in scalars:
+        if not (isinstance(s, torch.Tensor) and s.is_cuda and s.dtype == torch.float32 and s.numel() == 1):
+            raise TypeError("step_meter: every scalar must be a single-element fp32 GPU tensor")
+    _chk(ring, "ring", torch.int32)
+    if ring.dim() != 2 or ring.shape[1] != METER_ROW_WORDS or ring.shape[0] < 1:
+        raise ValueError("step_meter: the ring must be (rows >= 1, %d) int32" % METER_ROW_WORDS)
+    if not (opt_state.is_cuda and opt_state.is_contiguous() and opt_state.numel() * opt_state.element_size() >= 24):
+        raise ValueError("step_meter: opt_state must be the optimizer's contiguous device state block")
+    tab = (ctypes.c_void_p * len(scalars))(*[s.data_ptr() for s in scalars])
+    _ffi.call("demf_step_meter", len(scalars), ctypes.addressof(tab), _p(opt_state), float(grad_scale),
+              float(max_norm), _p(ring), int(ring.shape[0]), _stream())

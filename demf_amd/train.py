@@ -1,0 +1,340 @@
+"""The training loop and its command line: what the reference's ``train.py`` does through mmcv's EpochBasedRunner.
+
+  python -m demf_amd.train --data-root R --ann-file sunrgbd_infos_train.pkl --work-dir W
+                           [--val-ann-file sunrgbd_infos_val.pkl] [--load-from C] [--resume-from C] [--no-validate]
+                           [--no-graphs] [--batch-size 16] [--epochs 36] [--seed 0] [--workers 4] [--log-interval 50]
+
+``fit`` feeds a dataset through ``SceneLoader(mode="train")``, the frozen image stream and ``engine.Trainer`` (one
+captured hipGraph per batch shape, ``StepCache``).  Losses, gradient norm and learning rate are logged through the
+device-side step meter (``meter.StepMeter``): the loop enqueues one copy of the meter's ring per log interval and
+never waits for the GPU between log points.  Checkpoints are written per epoch, as mmcv's CheckpointHook does, in
+a layout ``infer.load_checkpoint`` and the reference's tools read; ``resume_from`` continues with the next epoch
+(mmcv's resume granularity).  Validation is ``infer.run_test`` + ``dataset.evaluate``.
+
+Single process, one GPU.  Multi-rank training (the reference's tools/dist_train.sh) is not part of this module.
+"""
+import argparse
+import functools
+import glob
+import json
+import math
+import os
+import re
+import sys
+import time
+
+import torch
+
+# The reference's values, where it sets them:
+DEFAULTS = dict(
+    batch_size=16,           # configs/_base_/datasets/sunrgbd-3d-10class.py:75  samples_per_gpu=16
+    workers=4,               # configs/_base_/datasets/sunrgbd-3d-10class.py:76  workers_per_gpu=4
+    repeat=5,                # configs/_base_/datasets/sunrgbd-3d-10class.py:77-86  RepeatDataset(times=5)
+    lr=0.008,                # configs/_base_/schedules/schedule_3x.py:4-5  AdamW lr=0.008
+    weight_decay=0.01,       # configs/_base_/schedules/schedule_3x.py:5  weight_decay=0.01
+    max_grad_norm=10,        # configs/_base_/schedules/schedule_3x.py:6  grad_clip max_norm=10, norm_type=2
+    lr_steps=(24, 32),       # configs/_base_/schedules/schedule_3x.py:7  policy='step', step=[24, 32]
+    gamma=0.1,               # (mmcv StepLrUpdaterHook's default, which schedule_3x.py:7 leaves in place)
+    max_epochs=36,           # configs/_base_/schedules/schedule_3x.py:9  EpochBasedRunner max_epochs=36
+    ckpt_interval=1,         # configs/_base_/default_runtime.py:1, configs/demf/demf_votenet.py:280  interval=1
+    max_keep_ckpts=1,        # configs/demf/demf_votenet.py:280  checkpoint_config max_keep_ckpts=1
+    log_interval=50,         # configs/_base_/default_runtime.py:6-7  log_config interval=50
+    eval_interval=36,        # configs/demf/demf_votenet.py:275-278  evaluation interval=36
+    seed=0,
+)
+
+
+def lr_factor(epoch, lr_steps=DEFAULTS["lr_steps"], gamma=DEFAULTS["gamma"]):
+    """mmcv StepLrUpdaterHook by epoch (0-based, as ``runner.epoch``): gamma ** (milestones reached).  The same
+    expression as ``engine.Trainer.set_epoch``."""
+    return gamma ** sum(1 for s in lr_steps if epoch >= s)
+
+
+def loader_epoch(epoch, rep, repeat):
+    """The ``SceneLoader.epoch`` of pass ``rep`` (0 .. repeat-1) of runner epoch ``epoch`` (0-based): every pass of
+    the run has its own number, so a resumed run draws the permutations and augmentations the first one would."""
+    if not 0 <= rep < repeat:
+        raise ValueError(f"pass {rep} of {repeat}")
+    return int(epoch) * int(repeat) + int(rep)
+
+
+def format_log(rows, epoch, it, base_lr, seconds_per_iter, names=None):
+    """One ``mode: "train"`` log line from the meter rows of an interval: ``epoch`` (1-based) and ``iter`` (global,
+    1-based) of the interval's last step, ``lr`` of the first parameter group, the mean of every loss term, of
+    ``loss`` (the meter's ``_total``) and of ``grad_norm`` over the rows, ``time`` per iteration."""
+    if not rows:
+        raise ValueError("a log line needs at least one meter row")
+    skip = ("t", "lr_factor", "grad_norm", "clip", "nonfinite", "_total")
+    names = [k for k in rows[0] if k not in skip] if names is None else [k for k in names if k != "_total"]
+    line = dict(mode="train", epoch=int(epoch), iter=int(it), lr=float(base_lr) * rows[-1]["lr_factor"])
+    n = len(rows)
+    for k in names:
+        line[k] = math.fsum(r[k] for r in rows) / n
+    line["loss"] = math.fsum(r["_total"] for r in rows) / n
+    line["grad_norm"] = math.fsum(r["grad_norm"] for r in rows) / n
+    line["time"] = float(seconds_per_iter)
+    return line
+
+
+def check_finite(rows, iters_per_epoch):
+    """Stop the run at the first metered step with a non-finite loss term or gradient norm."""
+    for r in rows:
+        if r["nonfinite"]:
+            it = r["t"] + 1
+            raise FloatingPointError("non-finite %s at epoch %d, iteration %d (optimizer step %d)"
+                                     % (", ".join(r["nonfinite"]), r["t"] // max(iters_per_epoch, 1) + 1, it, r["t"]))
+
+
+# ---- checkpoints --------------------------------------------------------------------------------------------------
+def _to_cpu(v):
+    if torch.is_tensor(v):
+        return v.detach().cpu()
+    if isinstance(v, dict):
+        return {k: _to_cpu(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return type(v)(_to_cpu(x) for x in v)
+    return v
+
+
+def make_checkpoint(model, trainer, meter, meta):
+    """{"meta", "state_dict", "trainer", "meter"}: ``state_dict`` is the model's, under the key mmcv uses, so that
+    ``infer.load_checkpoint`` and the reference's tools read the file; ``trainer`` is ``Trainer.state_dict()``
+    without its copy of the model.  Tensors, numbers, strings and containers only (``torch.load(weights_only=True)``)."""
+    tsd = dict(trainer.state_dict())
+    tsd.pop("model")
+    return _to_cpu(dict(meta=dict(meta), state_dict=dict(model.state_dict()), trainer=tsd,
+                        meter=None if meter is None else meter.state_dict()))
+
+
+def restore_checkpoint(ckpt, model, trainer, meter=None):
+    """Model, optimizer (moments, step count, lr factor), dropout counter and meter position -> ``meta``."""
+    trainer.load_state_dict(dict(ckpt["trainer"], model=ckpt["state_dict"]))
+    if meter is not None and ckpt.get("meter") is not None:
+        meter.load_state_dict(ckpt["meter"])
+    return ckpt["meta"]
+
+
+def _atomic_save(obj, path):
+    tmp = path + ".tmp"
+    torch.save(obj, tmp)
+    os.replace(tmp, path)                       # (a reader sees the old file or the whole new one)
+
+
+def save_checkpoint(work_dir, epoch, ckpt, max_keep_ckpts=DEFAULTS["max_keep_ckpts"]):
+    """``epoch_{epoch}.pth`` (written under a temporary name and renamed), then ``latest.pth`` the same way, then
+    every ``epoch_*.pth`` but the newest ``max_keep_ckpts`` is deleted (``max_keep_ckpts`` <= 0 keeps all)."""
+    os.makedirs(work_dir, exist_ok=True)
+    path = os.path.join(work_dir, f"epoch_{int(epoch)}.pth")
+    _atomic_save(ckpt, path)
+    _atomic_save(ckpt, os.path.join(work_dir, "latest.pth"))
+    if max_keep_ckpts > 0:
+        found = []
+        for p in glob.glob(os.path.join(work_dir, "epoch_*.pth")):
+            m = re.fullmatch(r"epoch_(\d+)\.pth", os.path.basename(p))
+            if m:
+                found.append((int(m.group(1)), p))
+        for _, p in sorted(found)[:-max_keep_ckpts]:
+            os.remove(p)
+    return path
+
+
+def load_checkpoint_file(path):
+    return torch.load(path, map_location="cpu", weights_only=True)
+
+
+# ---- the loop -----------------------------------------------------------------------------------------------------
+def _lookahead(it):
+    """(item, next item or None) pairs."""
+    it = iter(it)
+    try:
+        cur = next(it)
+    except StopIteration:
+        return
+    for nxt in it:
+        yield cur, nxt
+        cur = nxt
+    yield cur, None
+
+
+class _Log:
+    def __init__(self, path, echo=True):
+        self.f = open(path, "a")
+        self.echo = echo
+
+    def write(self, line):
+        text = json.dumps(line)
+        self.f.write(text + "\n")
+        self.f.flush()
+        if self.echo:
+            print(text, flush=True)
+
+    def close(self):
+        self.f.close()
+
+
+def validate(model, val_set, batch_size, workers, num_points, img_scale, seed=0):
+    """One validation pass: ``infer.run_test`` into a fresh store, ``val_set.evaluate``; the model goes back to
+    ``train()`` (for ``DeMFVoteNet`` that keeps the image branch in eval)."""
+    from . import infer
+    try:
+        store = infer.run_test(model, val_set, batch_size=batch_size, workers=workers, num_points=num_points,
+                               img_scale=img_scale, seed=seed)
+        return val_set.evaluate(store)
+    finally:
+        model.train()
+
+
+def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_size"],
+        max_epochs=DEFAULTS["max_epochs"], repeat=DEFAULTS["repeat"], lr=DEFAULTS["lr"],
+        weight_decay=DEFAULTS["weight_decay"], max_grad_norm=DEFAULTS["max_grad_norm"],
+        lr_steps=DEFAULTS["lr_steps"], gamma=DEFAULTS["gamma"], log_interval=DEFAULTS["log_interval"],
+        ckpt_interval=DEFAULTS["ckpt_interval"], max_keep_ckpts=DEFAULTS["max_keep_ckpts"],
+        eval_interval=DEFAULTS["eval_interval"], seed=DEFAULTS["seed"], workers=DEFAULTS["workers"], graphs=True,
+        resume_from=None, load_from=None, num_points=20000, img_scale=(1333, 800), on_step=None, echo=True,
+        val_batch_size=None):
+    """Train ``model`` (a ``DeMFVoteNet``: frozen image stream + hot path) on ``train_set`` for ``max_epochs`` runner
+    epochs of ``repeat`` passes each.  -> dict(trainer, meter, stepper, epoch, iter, val).
+
+    ``on_step(info)``: called after every step has been enqueued, ``info = dict(epoch, iter, indices, loss)`` with
+    the 1-based epoch and global iteration, the batch's dataset indices and the step's loss as a DEVICE tensor
+    (reading it synchronises; the loop itself does not)."""
+    from . import engine, infer
+    from .meter import StepMeter, loss_names
+    from .modules import DeMFHotPath
+    from .pipeline import SceneLoader
+    if batch_size < 1 or max_epochs < 0 or repeat < 1 or log_interval < 1 or ckpt_interval < 1 or eval_interval < 1:
+        raise ValueError("batch_size, repeat, log_interval, ckpt_interval and eval_interval must be positive")
+    if not hasattr(model, "extract_img_feat"):
+        raise TypeError("fit() trains a detector with an image stream (DeMFVoteNet): the loader yields images")
+    os.makedirs(work_dir, exist_ok=True)
+    torch.manual_seed(seed)                       # (the Trainer seeds the dropout counter from it)
+    model.cuda().train()
+    if load_from is not None:
+        # weights only (mmcv's load_from): through the model's load_state_dict, which for DeMFVoteNet applies the
+        # stage-1 image-branch key remap; a stage-1 file holds the image branch alone, so not strict
+        bad = model.load_state_dict(infer._model_state(load_checkpoint_file(load_from)), strict=False)
+        if echo:
+            print(f"load_from {load_from}: {len(bad.missing_keys)} missing, {len(bad.unexpected_keys)} unexpected keys",
+                  flush=True)
+    # the runner computes the frozen image features itself and drives the hot path's forward_train
+    trainer = engine.Trainer(model, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                             forward=functools.partial(DeMFHotPath.forward_train, model))
+    names = loss_names()
+    meter = StepMeter(names, ring_rows=max(128, 2 * log_interval))
+    trainer.attach_meter(meter)
+    epoch0, it = 0, 0
+    if resume_from is not None:
+        meta = restore_checkpoint(load_checkpoint_file(resume_from), model, trainer, meter)
+        epoch0, it = int(meta["epoch"]), int(meta["iter"])
+    stepper = trainer.bucketed() if graphs else None
+    loader = SceneLoader(train_set, batch_size, "train", seed=seed, img_scale=img_scale, num_points=num_points,
+                         workers=workers)
+    ipe = repeat * len(loader)                    # iterations per runner epoch
+    log = _Log(os.path.join(work_dir, "train.log.json"), echo)
+    rows, marks = [], []                          # meter rows not logged yet; (last t, epoch, iter, s/iter) per interval
+
+    def drain(wait):
+        got = meter.collect(wait=wait)
+        check_finite(got, ipe)
+        rows.extend(got)
+        while marks and rows and rows[-1]["t"] >= marks[0][0]:
+            last_t, e, i, dt = marks.pop(0)
+            k = sum(1 for r in rows if r["t"] <= last_t)
+            log.write(format_log(rows[:k], e, i, lr, dt, names))
+            del rows[:k]
+
+    val = None
+    try:
+        for epoch in range(epoch0, max_epochs):
+            trainer.set_epoch(epoch, lr_steps, gamma)
+            since, t_mark = 0, time.perf_counter()
+
+            def mark():
+                nonlocal since, t_mark
+                now = time.perf_counter()
+                meter.snapshot()
+                marks.append((it - 1, epoch + 1, it, (now - t_mark) / since))
+                since, t_mark = 0, now
+
+            for rep in range(repeat):
+                loader.epoch = loader_epoch(epoch, rep, repeat)
+                for batch, nxt in _lookahead(loader):
+                    feats = model.extract_img_feat(batch["img"], batch["img_metas"])
+                    step_batch = dict(points=batch["points"], img_features=feats, img_metas=batch["img_metas"],
+                                      gt_bboxes_3d=batch["gt_bboxes_3d"], gt_labels_3d=batch["gt_labels_3d"])
+                    if stepper is not None:
+                        loss = stepper.step(step_batch, next_points=None if nxt is None else nxt["points"])
+                    else:
+                        loss = trainer.step(step_batch)
+                    it += 1
+                    since += 1
+                    if on_step is not None:
+                        on_step(dict(epoch=epoch + 1, iter=it, indices=tuple(batch.indices), loss=loss))
+                    if since >= log_interval:
+                        mark()
+                    drain(False)
+            if since:
+                mark()                            # the tail of the epoch
+            drain(True)
+            done = epoch + 1
+            if done % ckpt_interval == 0 or done == max_epochs:
+                meta = dict(epoch=done, iter=it, seed=int(seed), repeat=int(repeat), batch_size=int(batch_size),
+                            lr=float(lr), lr_steps=[int(s) for s in lr_steps], gamma=float(gamma),
+                            max_epochs=int(max_epochs))
+                save_checkpoint(work_dir, done, make_checkpoint(model, trainer, meter, meta), max_keep_ckpts)
+            if val_set is not None and (done % eval_interval == 0 or done == max_epochs):
+                trainer.flush()
+                val = validate(model, val_set, val_batch_size or batch_size, workers, num_points, img_scale, seed)
+                log.write(dict(mode="val", epoch=done, iter=it, **val))
+    finally:
+        log.close()
+    return dict(trainer=trainer, meter=meter, stepper=stepper, epoch=max(epoch0, max_epochs), iter=it, val=val)
+
+
+# ---- command line -------------------------------------------------------------------------------------------------
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(prog="python -m demf_amd.train", description=__doc__.split("\n")[0])
+    p.add_argument("--data-root", required=True)
+    p.add_argument("--ann-file", required=True, help="training infos file, absolute or relative to --data-root")
+    p.add_argument("--work-dir", required=True, help="checkpoints and train.log.json go here")
+    p.add_argument("--val-ann-file", default=None, help="validation infos file (none: no validation)")
+    p.add_argument("--load-from", default=None, help="weights to start from (for example a stage-1 image checkpoint)")
+    p.add_argument("--resume-from", default=None, help="a checkpoint of this runner: continue with its next epoch")
+    p.add_argument("--no-validate", action="store_true")
+    p.add_argument("--no-graphs", action="store_true", help="eager steps instead of captured hipGraphs")
+    p.add_argument("--batch-size", type=int, default=DEFAULTS["batch_size"])
+    p.add_argument("--epochs", type=int, default=DEFAULTS["max_epochs"])
+    p.add_argument("--seed", type=int, default=DEFAULTS["seed"])
+    p.add_argument("--workers", type=int, default=DEFAULTS["workers"])
+    p.add_argument("--log-interval", type=int, default=DEFAULTS["log_interval"])
+    args = p.parse_args(argv)
+    if args.batch_size < 1 or args.workers < 1 or args.log_interval < 1:
+        p.error("--batch-size, --workers and --log-interval must be positive")
+    if args.epochs < 0:
+        p.error("--epochs must not be negative")
+    if args.load_from and args.resume_from:
+        p.error("--load-from and --resume-from exclude each other (a resumed run takes its weights from the checkpoint)")
+    return args
+
+
+def main(argv=None, model=None, **fit_kwargs):
+    """-> what ``fit`` returns.  ``model``: the detector to train instead of the full-size ``DeMFVoteNet()``;
+    ``fit_kwargs`` go to ``fit`` (``num_points``, ``img_scale``, schedule overrides, ``on_step``)."""
+    args = parse_args(argv)
+    from .dataset import SUNRGBDDataset
+    train_set = SUNRGBDDataset(args.data_root, args.ann_file)
+    val_set = None
+    if args.val_ann_file and not args.no_validate:
+        val_set = SUNRGBDDataset(args.data_root, args.val_ann_file, test_mode=True)
+    if model is None:
+        from .modules import DeMFVoteNet
+        model = DeMFVoteNet()
+    kw = dict(val_set=val_set, batch_size=args.batch_size, max_epochs=args.epochs, seed=args.seed,
+              workers=args.workers, log_interval=args.log_interval, graphs=not args.no_graphs,
+              resume_from=args.resume_from, load_from=args.load_from)
+    kw.update(fit_kwargs)
+    return fit(model, train_set, args.work_dir, **kw)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

@@ -894,6 +894,26 @@ DEMF_INTERNAL int demf_adamw_state_f32(int nseg, const long long* seg_start, con
                          float* exp_avg_sq, void* opt_state, float max_norm, float grad_scale, float beta1,
                          float beta2, float eps, demf_stream_t stream);
 
+/* Step meter (csrc/meter.hip): one record per optimizer step in a device-resident ring of `rows` rows, written
+ * by one wave between the launch that completes opt_state.sumsq and the demf_adamw_state_f32 launch that clears
+ * it (same stream, or a node of the same hipGraph).  Row t % rows, 16 words of 4 bytes:
+ *   word 0-1  int64  t           opt_state.t at the launch = optimizer steps completed before this one (the stamp)
+ *   word 2    uint32 flags       bit i (i < 10): scalar i is NaN or +-Inf; DEMF_METER_FLAG_GRAD_NORM: grad_norm is
+ *   word 3    float  lr_factor   opt_state.lr_factor
+ *   word 4    float  grad_norm   (float)sqrt(sumsq) * grad_scale: the norm before clipping (mmcv's `grad_norm`)
+ *   word 5    float  clip        min(1, max_norm / (grad_norm + 1e-6)), the expression of demf_adamw_state_f32
+ *                                (1 when max_norm <= 0)
+ *   word 6-15 float  scalar 0 .. n-1 as read (non-finite values included), 0 in the unused slots
+ * scalars: HOST array of n (1..10) DEVICE pointers to single floats, anywhere (views into a loss vector are
+ * fine); they are passed by value in the kernel arguments.  grad_scale / max_norm: the values the AdamW launch
+ * of the same step gets.  The launch only reads opt_state; every other row of the ring is left alone.        */
+#define DEMF_METER_ROW_WORDS 16
+#define DEMF_METER_HEAD_WORDS 6
+#define DEMF_METER_MAX_SCALARS 10
+#define DEMF_METER_FLAG_GRAD_NORM (1u << 16)
+DEMF_INTERNAL int demf_step_meter(int n, const float* const* scalars, const void* opt_state, float grad_scale,
+                    float max_norm, void* ring, int rows, demf_stream_t stream);
+
 /* ------------------------------------------------------------------ *
  * Dense blocks of the DeMF fusion decoder layer (csrc/dense.hip)
  * Reference: demf/modeling/layers/transformer.py:55-80 -> mmcv DetrTransformerDecoderLayer
