@@ -50,7 +50,7 @@ __device__ __forceinline__ float ce(const float* p, int n, int t, float* grad /*
 struct IoU {
   float iou, overlap, uni;
   float lo[3], hi[3];          // intersection bounds
-  bool pos[3];                 // intersection extent > 0 per axis
+  bool pos[3];                 // extent >= 0 per axis: where clamp(min=0) passes the gradient (AT 0 too)
   bool clamped;                // union was clamped to eps
 };
 
@@ -65,7 +65,9 @@ __device__ __forceinline__ IoU aa_iou(const float* c, const float* s, const floa
     r.lo[k] = fmaxf(l1, l2);
     r.hi[k] = fminf(h1, h2);
     const float w = r.hi[k] - r.lo[k];
-    r.pos[k] = w > 0.f;
+    // torch's clamp backward masks with x >= min: boxes that exactly touch on one axis (extent 0, overlap 0)
+    // still get d overlap / d extent = the product of the other two extents
+    r.pos[k] = w >= 0.f;
     ov *= fmaxf(w, 0.f);
   }
   r.overlap = ov;

@@ -151,13 +151,26 @@ def test_captured_step_is_this_librarys_kernels():
     for _ in range(2):
         replay()
     torch.cuda.synchronize()
+
+    def profiled_replay():
+        # two replays, each waited for: with ONE replay launched right behind the opening of the window, the window
+        # came back without any kernel of the replay whenever the loss-edge tests had run earlier in the same process
+        # (and held them when they had not); with two it holds them either way
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            for _ in range(2):
+                tr._graph.replay()
+                torch.cuda.synchronize()
+        names = {str(e.key): int(e.count) for e in prof.key_averages()}
+        return {n: c for n, c in names.items() if "(" in n or n.startswith("__amd")}
+
     p0 = tr.opt.flat.clone()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        tr._graph.replay()
-        torch.cuda.synchronize()
+    kernels = profiled_replay()
     assert not torch.equal(p0, tr.opt.flat), "the graph alone must have updated the parameters"
-    names = {str(e.key): int(e.count) for e in prof.key_averages()}
-    kernels = {n: c for n, c in names.items() if "(" in n or n.startswith("__amd")}
+    for attempt in range(3):            # late in a long process a window now and then comes back empty: look again
+        if any("demf::" in n for n in kernels):
+            break
+        print("profiler window %d: %d kernel names, none of this library: %s" % (attempt, len(kernels), sorted(kernels)[:6]))
+        kernels = profiled_replay()
     if not any("demf::" in n for n in kernels):
         pytest.skip("the profiler recorded no kernels of the graph replay on this runtime")
     joined = "\n".join(sorted(kernels))
