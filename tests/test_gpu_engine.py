@@ -105,9 +105,11 @@ def test_full_size_replays_stay_finite(prefetch):
 
 
 def test_flat_adamw_matches_torch_adamw():
-    """demf_adamw_f32 (clip folded in) == clip_grad_norm_ + torch.optim.AdamW on the CPU, the
-    optimizer the reference's runner uses (schedule_3x.py:6-7), over several steps and both
-    parameter groups.  Tolerance 2e-6 absolute on parameters of magnitude <= 1."""
+    """Trainer._update - FlatAdamW.step: demf_sumsq_f32 + ONE demf_adamw_state_f32 launch over both
+    groups, clip folded in - == clip_grad_norm_ + torch.optim.AdamW on the CPU, the optimizer the
+    reference's runner uses (schedule_3x.py:6-7), over several steps and both parameter groups.
+    Tolerance 2e-6 absolute on parameters of magnitude <= 1.  (The per-group entry point
+    demf_adamw_f32 is launched by tests/test_gpu_optim_edges.py.)"""
     import copy
     from demf_amd import engine
     torch.manual_seed(0)
