@@ -89,6 +89,9 @@ SIGNATURES = {
     "demf_sumsq_f32": [ctypes.c_longlong, _ptr, _ptr, _ptr],
     "demf_adamw_state_f32": [_c_int] + [_ptr] * 9 + [_c_float] * 5 + [_ptr],
     "demf_step_meter": [_c_int, _ptr, _ptr, _c_float, _c_float, _ptr, _c_int, _ptr],
+    "demf_multi_add": [_c_int, _ptr, _c_int, _ptr],
+    "demf_multi_add_sumsq": [_c_int, _ptr, _c_int, _ptr, _ptr],
+    "demf_scalars_accum": [_c_int, _ptr, _ptr, _c_float, _ptr],
     "demf_mlp_gemm_fwd": [_c_int] * 4 + [_ptr] * 6,
     "demf_mlp_gemm_fwd_pool": [_c_int] * 4 + [_ptr] * 5 + [_c_int] + [_ptr] * 5,
     "demf_mlp_gemm_fwd_bn": [_c_int] * 4 + [_ptr] * 7 + [_c_float, _c_float] + [_ptr] * 7,

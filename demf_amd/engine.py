@@ -102,6 +102,8 @@ class FlatGrads:
         self._pending_tables, self._tables = [], []     # address tables of captured pack launches
         self.captured_pack = False      # set by Trainer.capture around its captures (it calls finish_capture)
         self.sumsq_state = None         # FlatAdamW.state while a capture wants the pack to take the clip norm
+        self.mode = None                # gradient accumulation (Trainer(accumulate > 1)): "accumulate" / "last" - the
+        #                                 pack ADDS into the buffer; None: it overwrites (one pass per optimizer step)
         self._reserved_table = None
         off = 0
         for p in self.params:
@@ -119,6 +121,8 @@ class FlatGrads:
                 grads = torch.autograd.grad(loss, self.params, allow_unused=True)
         else:
             grads = torch.autograd.grad(loss, self.params, allow_unused=True)
+        if self.mode is not None:
+            return self._add_into(grads)
         dst = [v for v, g in zip(self.views, grads) if g is not None]
         src = [g for g in grads if g is not None]
         if len(src) != len(grads):
@@ -146,6 +150,34 @@ class FlatGrads:
             self._pending_tables.append((table, tab))
             return
         torch._foreach_copy_(dst, src)
+
+    def _add_into(self, grads):
+        """One pass of a group of micro-steps: flat += grads.  The buffer is zero at the start of a group
+        (Trainer's invariant), nothing is zero-filled here - a ``None`` gradient leaves the earlier passes' sum
+        alone.  Captured: one demf_multi_add launch; the last pass's table covers EVERY parameter (null sources
+        for ``None`` gradients) so that demf_multi_add_sumsq takes the norm of the whole accumulated buffer."""
+        if self.captured_pack and self.flat.is_cuda and torch.cuda.is_current_stream_capturing():
+            from . import _ffi
+            with_sum = self.mode == "last" and self.sumsq_state is not None
+            pairs = [(g, d) for g, d in zip(grads, self.views) if g is not None or with_sum]
+            if not pairs:
+                return
+            src = [g if g is None or g.is_contiguous() else g.contiguous() for g, _ in pairs]
+            tab = [[0 if g is None else g.data_ptr() for g in src], [d.data_ptr() for _, d in pairs],
+                   [d.numel() for _, d in pairs]]
+            table = self._reserved_table.view(-1)[:3 * len(src)].view(3, len(src))
+            blocks = max(1, min(64, max(tab[2]) // 4096))
+            stream = torch.cuda.current_stream().cuda_stream
+            if with_sum:
+                _ffi.call("demf_multi_add_sumsq", len(src), table.data_ptr(), blocks, self.sumsq_state.data_ptr(),
+                          stream)
+            else:
+                _ffi.call("demf_multi_add", len(src), table.data_ptr(), blocks, stream)
+            self._pending_tables.append((table, tab))
+            return
+        dst = [v for v, g in zip(self.views, grads) if g is not None]
+        if dst:
+            torch._foreach_add_(dst, [g for g in grads if g is not None])
 
     def reserve_table(self):
         """Room for the address table of one captured pack launch, from the ordinary allocator."""
@@ -306,9 +338,20 @@ def _gc_paused():
 class Trainer:
     """fwd -> loss -> bwd -> one all-reduce -> clip -> AdamW, as one callable step."""
 
-    def __init__(self, model, lr=0.008, weight_decay=0.01, max_grad_norm=10.0, forward=None):
+    _accumulate, micro, _loss_acc = 1, 0, None        # (gradient accumulation off: the plain step)
+
+    def __init__(self, model, lr=0.008, weight_decay=0.01, max_grad_norm=10.0, forward=None, accumulate=1):
         """``forward``: called instead of ``model.forward_train`` with the same arguments (a detector whose own
-        ``forward_train`` takes the image runs its hot path through this: demf_amd/train.py)."""
+        ``forward_train`` takes the image runs its hot path through this: demf_amd/train.py).
+        ``accumulate`` = W: one optimizer step is formed from W micro-steps (``step`` / a replay = ONE forward +
+        backward on one batch), AdamW on the mean of their gradients - the reference's 8 ranks x 16 scenes
+        (tools/dist_train.sh:4) on one GPU with W = 8.  ``micro`` (0 .. W-1, host side) is the position in the open
+        group.  Between optimizer steps the flat gradient buffer, the loss accumulator, the state's ``sumsq`` and
+        its ticket are all zero; the last micro-step clears them after AdamW has consumed them.  W = 1 is the plain
+        step."""
+        self._accumulate = self._check_accumulate(accumulate)
+        self.micro = 0
+        self._loss_acc = None              # with a meter and W > 1: the group's mean loss scalars, on the device
         self.model = model
         self._forward = forward
         self.meter = None
@@ -333,6 +376,79 @@ class Trainer:
             torch.optim.AdamW(groups, lr=lr, weight_decay=weight_decay, foreach=True)
         self._base_lrs = [float(g["lr"]) for g in groups]
 
+    # ---- gradient accumulation ------------------------------------------------------------------------
+    @staticmethod
+    def _check_accumulate(value):
+        if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+            raise ValueError("accumulate must be a positive integer, got %r" % (value,))
+        return int(value)
+
+    @property
+    def accumulate(self):
+        return self._accumulate
+
+    @accumulate.setter
+    def accumulate(self, value):
+        value = self._check_accumulate(value)
+        if value == self._accumulate:
+            return
+        if self.micro:
+            raise RuntimeError("accumulate cannot change inside a group (micro = %d of %d): finish it or call "
+                               "reset_accumulation()" % (self.micro, self._accumulate))
+        if self.fused:
+            self.flush()
+        self._accumulate = value
+        self._ensure_acc()
+        self.reset_accumulation()          # (the plain step overwrites the buffer and may leave anything in it)
+
+    def _ensure_acc(self):
+        if self._accumulate > 1 and self.meter is not None and self._loss_acc is None:
+            from . import ops
+            self._loss_acc = torch.zeros(ops.METER_MAX_SCALARS, dtype=torch.float32, device=self.flat.flat.device)
+
+    def _acc_scalars(self):
+        return [self._loss_acc[i:i + 1] for i in range(len(self.meter.names))]
+
+    def reset_accumulation(self):
+        """Abandon the open group: gradient buffer, loss accumulator, ``sumsq`` and ticket back to zero,
+        ``micro = 0``.  Runs by itself when a forward + backward raises (outside capture), in ``load_state_dict``
+        and whenever the runner drops an incomplete group."""
+        self.micro = 0
+        if self._accumulate == 1:
+            return
+        self.flat.flat.zero_()
+        if self._loss_acc is not None:
+            self._loss_acc.zero_()
+        if self.fused:
+            self.opt.state[0:8].zero_()
+            self.opt.state[16:20].zero_()
+
+    def _mid_group(self, what):
+        if self.micro:
+            raise RuntimeError("%s in the middle of a group of micro-steps (micro = %d of accumulate = %d): finish "
+                               "the group or call reset_accumulation()" % (what, self.micro, self._accumulate))
+
+    def _refuse_overlap(self):
+        if self._accumulate > 1 and self.fused and self.allreduce_config()[2]:
+            raise RuntimeError("the overlapped (deferred) update is not available with accumulate = %d > 1: unset "
+                               "DEMF_AR_OVERLAP / allreduce_overlap" % self._accumulate)
+
+    def _clear_group(self):
+        """The clears of a group's last micro-step, behind the AdamW launch that consumed the buffers (kernel
+        launches: in the stream of an eager step, nodes of a captured one)."""
+        from . import _ffi
+        stream = torch.cuda.current_stream().cuda_stream
+        _ffi.call("demf_zero_f32", self.flat.flat.numel(), self.flat.flat.data_ptr(), stream)
+        if self.meter is not None:
+            _ffi.call("demf_zero_f32", self._loss_acc.numel(), self._loss_acc.data_ptr(), stream)
+
+    def _accumulate_scalars(self, scalars=None):
+        """acc += loss scalars / W (one demf_scalars_accum launch); without a meter there is no launch."""
+        if self.meter is not None:
+            from . import ops
+            ops.scalars_accum(self._loss_scalars if scalars is None else scalars,
+                              self._loss_acc, 1.0 / self._accumulate)
+
     def attach_meter(self, meter):
         """Meter every optimizer step from now on (meter.StepMeter over ``meter.loss_names()``): one
         ``demf_step_meter`` launch per step in front of the AdamW launch - in the stream of an eager update, as a
@@ -342,15 +458,18 @@ class Trainer:
         if meter is not None and not self.fused:
             raise RuntimeError("attach_meter: the step meter is a device kernel; this trainer runs the CPU / gloo "
                                "path (torch.optim.AdamW), which has nothing to meter")
+        self._mid_group("attach_meter()")
         if meter is not None:
             self.flush()
             meter.next_t = self.opt.t
         self.meter = meter
         self._loss_scalars = self._pending_scalars = None
+        self._ensure_acc()
 
     def set_epoch(self, epoch, steps=(24, 32), gamma=0.1):
         """The reference's step schedule (configs/_base_/schedules/schedule_3x.py:7-9:
         lr_config = dict(policy='step', step=[24, 32]), 36 epochs): lr x gamma at each milestone."""
+        self._mid_group("set_epoch()")
         factor = gamma ** sum(1 for s in steps if epoch >= s)
         if self.fused:
             self.flush()                 # (an overlapped step's owed update still uses the old rate)
@@ -364,6 +483,7 @@ class Trainer:
         """Model + optimizer state for resume (mmcv CheckpointHook, cfg:280), plus the dropout
         counter [seed, step] of the fused decoder layer so that a resumed run continues the mask
         sequence instead of replaying it from step 0."""
+        self._mid_group("state_dict()")
         if self.fused:
             self.flush()
         sd = dict(model=self.model.state_dict(), optimizer=self.opt.state_dict())
@@ -381,6 +501,7 @@ class Trainer:
         if self.fused and sd.get("dropout_rng") is not None:
             from . import fused
             fused.set_rng_state(self.flat.flat.device, sd["dropout_rng"])
+        self.reset_accumulation()
 
     def _fwd(self, batch, geometry=None):
         kw = {} if geometry is None else dict(geometry=geometry)
@@ -416,6 +537,8 @@ class Trainer:
             if self.fused and not torch.cuda.is_current_stream_capturing():
                 from . import ops
                 ops.reset_accumulators()          # (a step that raised half-way leaves BatchNorm sums behind)
+            if self._accumulate > 1 and not (self.fused and torch.cuda.is_current_stream_capturing()):
+                self.reset_accumulation()         # (the group this pass belonged to is abandoned)
             raise
         finally:
             self._arena(False)
@@ -467,6 +590,12 @@ class Trainer:
     def _finish_update(self, norm_taken=False, scalars=None):
         world = dist.get_world_size() if dist.is_initialized() else 1
         # (the norm is that of the SUM over ranks; 1/world is applied in-kernel)
+        if self._accumulate > 1:
+            # ... and over the W passes of the group: 1 / (W * world); the meter reads the accumulated means
+            self.opt.step(self.max_grad_norm, 1.0 / (self._accumulate * world), norm_taken=norm_taken,
+                          meter=self.meter, scalars=None if self.meter is None else self._acc_scalars())
+            self._clear_group()
+            return
         if self.meter is None:
             self.opt.step(self.max_grad_norm, 1.0 / world, norm_taken=norm_taken)
             return
@@ -511,14 +640,37 @@ class Trainer:
             self._finish_update(scalars=scalars)
             return
         self.flat.all_reduce_mean()
+        if self._accumulate > 1:
+            self.flat.flat.mul_(1.0 / self._accumulate)
         self.flat.clip_(self.max_grad_norm)
         self.opt.step()
+        if self._accumulate > 1:
+            self.flat.flat.zero_()
 
     def step(self, batch):
+        """One micro-step: forward + backward on ``batch`` -> its loss.  With ``accumulate`` = 1 that is the whole
+        optimizer step.  With W > 1 micro-steps 0 .. W-2 only add into the flat gradient buffer (no norm, no
+        collective, no meter row, no AdamW); micro-step W-1 adds, takes the norm of the sum (over ranks too - the
+        collective runs only here), clips, runs AdamW with grad_scale = 1 / (W * world) and clears the group."""
         if self.fused:
             self.flush()
-        total = self._fwd_bwd(batch)
-        self._update()
+        if self._accumulate == 1:
+            total = self._fwd_bwd(batch)
+            self._update()
+            return total
+        self._refuse_overlap()
+        self._ensure_acc()
+        last = self.micro == self._accumulate - 1
+        self.flat.mode = "last" if last else "accumulate"
+        try:
+            total = self._fwd_bwd(batch)
+        finally:
+            self.flat.mode = None
+        if self.fused:
+            self._accumulate_scalars()
+        if last:
+            self._update()
+        self.micro = 0 if last else self.micro + 1
         return total
 
     @staticmethod
@@ -557,6 +709,14 @@ class Trainer:
         if self.fused:
             from . import fused
             rng = fused.get_rng_state(self.flat.flat.device)
+        if self._accumulate > 1:
+            # ... and, inside a group, what the earlier passes have accumulated: the warm-up passes ADD their
+            # gradients into the flat buffer (StepCache captures lazily, possibly at micro >= 1)
+            bufs.append((self.flat.flat, self.flat.flat.clone()))
+            if self._loss_acc is not None:
+                bufs.append((self._loss_acc, self._loss_acc.clone()))
+            if self.fused:
+                bufs.append((self.opt.state, self.opt.state.clone()))
 
         def restore():
             for b, c in bufs:
@@ -567,7 +727,7 @@ class Trainer:
         return restore
 
     def capture(self, batch, warmup=3, prefetch_geometry=True, max_gt=None, dry=False, geo_pipe=None,
-                update_in_graph=None):
+                update_in_graph=None, role=None):
         """Capture forward + loss + backward of ``batch`` (static shapes, device-resident
         inputs) into one hipGraph; returns ``replay(next_points=None)`` = graph launch + eager
         all-reduce / clip / AdamW.  The path issues no host sync or host->device copy after
@@ -606,8 +766,32 @@ class Trainer:
         optimizer's step count / learning-rate factor / norm live on the device (FlatAdamW.state), so a
         replay is the WHOLE step and nothing eager follows it.  With more than one rank the collective
         sits between backward and update and stays an eager RCCL call (``DEMF_GRAPH_ALLREDUCE=1``:
-        captured as well, where the runtime allows it)."""
+        captured as well, where the runtime allows it).
+        ``role`` (``accumulate`` > 1 only; default: from ``trainer.micro``): ``"accumulate"`` - the graph of a
+        micro-step 0 .. W-2: forward + backward + ONE demf_multi_add pack (+ one demf_scalars_accum node with a
+        meter); ``"last"`` - the graph of micro-step W-1: forward + backward + demf_multi_add_sumsq,
+        demf_scalars_accum, demf_step_meter reading the accumulator, demf_adamw_state_f32, the clears.  With
+        ``update_in_graph=False`` or more ranks the eager tail (norm, collective, meter, AdamW, clears) follows a
+        ``"last"`` replay only.  A replay refuses to run when its role does not match ``trainer.micro`` or when
+        ``accumulate`` has changed since the capture, and advances ``micro``.  Warm-up passes are always ``dry``
+        with W > 1: they must not touch the open group."""
         dev = batch["points"].device
+        W_c = self._accumulate
+        if W_c == 1:
+            if role not in (None, "last"):
+                raise ValueError("capture(role=%r): with accumulate = 1 every step is the last of its group" % (role,))
+            role = None
+        else:
+            if role is None:
+                role = "last" if self.micro == W_c - 1 else "accumulate"
+            if role not in ("accumulate", "last"):
+                raise ValueError("capture(role=%r): 'accumulate' or 'last'" % (role,))
+            if os.environ.get("DEMF_GEO_AT_BWD"):
+                raise RuntimeError("DEMF_GEO_AT_BWD=1 (forward and backward as two graphs) is not available with "
+                                   "accumulate = %d > 1" % W_c)
+            self._refuse_overlap()
+            self._ensure_acc()
+            dry = True
         world_c, stub_c, _ = self.allreduce_config()
         if update_in_graph is None:
             update_in_graph = bool(int(os.environ.get("DEMF_GRAPH_UPDATE", "1")))
@@ -645,11 +829,15 @@ class Trainer:
         restore = self._snapshot_state() if dry else None
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            for _ in range(warmup):
-                if dry:
-                    self._fwd_bwd(batch)
-                else:
-                    self.step(batch)
+            self.flat.mode = role
+            try:
+                for _ in range(warmup):
+                    if dry:
+                        self._fwd_bwd(batch)
+                    else:
+                        self.step(batch)
+            finally:
+                self.flat.mode = None
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         can_prefetch = prefetch_geometry and hasattr(self.model, "index_geometry")
@@ -695,11 +883,15 @@ class Trainer:
             loss = total.detach()
         else:
             self.flat.captured_pack = True
-            self.flat.sumsq_state = self.opt.state if (update_in_graph and world_c == 1) else None
+            self.flat.mode = role
+            self.flat.sumsq_state = self.opt.state if (update_in_graph and world_c == 1
+                                                       and role != "accumulate") else None
             try:
                 with _gc_paused(), torch.cuda.graph(graph):
                     loss = self._fwd_bwd(batch, static_geo)
-                    if update_in_graph:
+                    if role is not None:
+                        self._accumulate_scalars()
+                    if update_in_graph and role != "accumulate":
                         self._captured_update(world_c)
             except Exception:
                 if update_in_graph and world_c > 1:
@@ -707,13 +899,19 @@ class Trainer:
                     # (a second capture: the failed one left nothing behind)
                     self.flat.captured_pack = False
                     self.flat.sumsq_state = None
+                    self.flat.mode = None
+                    if restore is not None and role is not None:
+                        restore()                 # (the warm-up passes added into the open group)
                     return self.capture(static, warmup=0, prefetch_geometry=prefetch_geometry, max_gt=max_gt,
                                         dry=dry, geo_pipe=geo if geo is not None else geo_pipe,
-                                        update_in_graph=False)
+                                        update_in_graph=False, role=role)
+                if restore is not None and role is not None:
+                    restore()
                 raise
             finally:
                 self.flat.captured_pack = False
                 self.flat.sumsq_state = None
+                self.flat.mode = None
         self.flat.finish_capture()
         if restore is not None:
             restore()
@@ -726,6 +924,24 @@ class Trainer:
         one_deep = not os.environ.get("DEMF_GEO_TWO_DEEP")         # A/B: see replay()
 
         def replay(next_points=None):
+            """``run`` behind the gradient-accumulation checks: the role this step was captured in must be the one
+            ``trainer.micro`` asks for (last <=> micro == W-1) and ``accumulate`` must be what it was at the
+            capture; nothing has been touched when it refuses.  Advances ``micro``."""
+            if self._accumulate != W_c:
+                raise RuntimeError("this step was captured with accumulate = %d and the trainer now has accumulate "
+                                   "= %d: capture again" % (W_c, self._accumulate))
+            if role is None:
+                return run(next_points)
+            if (role == "last") != (self.micro == W_c - 1):
+                raise RuntimeError("this step was captured in the '%s' role and the trainer is at micro = %d of "
+                                   "accumulate = %d, which takes the '%s' role"
+                                   % (role, self.micro, W_c, "last" if self.micro == W_c - 1 else "accumulate"))
+            self._refuse_overlap()
+            out = run(next_points)
+            self.micro = 0 if role == "last" else self.micro + 1
+            return out
+
+        def run(next_points=None):
             """One training step.  Default (one-deep): ``next_points`` is the cloud of the NEXT batch;
             its coordinate pre-pass is launched on the side stream in front of the step's graph and
             runs underneath the forward (with ``DEMF_GEO_AT_BWD=1``: between the forward and the
@@ -748,8 +964,8 @@ class Trainer:
                     raise RuntimeError("this step was captured with its optimizer update inside the graph "
                                        "(world %d, no all-reduce stub); capture again with update_in_graph=False"
                                        % world_c)
-            update = (lambda defer=False: None) if update_in_graph else self._update if not metered else \
-                (lambda defer=False: self._update(defer, scalars=scalars))
+            update = (lambda defer=False: None) if (update_in_graph or role == "accumulate") else \
+                self._update if not metered else (lambda defer=False: self._update(defer, scalars=scalars))
             if can_prefetch and os.environ.get("DEMF_SKIP_GEO"):     # measurement only: the step alone
                 self.flush()
                 graph.replay()
@@ -837,6 +1053,8 @@ class Trainer:
                 head.refresh_metas(static["img_metas"], new["img_metas"])
 
         replay.load = load
+        replay.role = role
+        replay.accumulate = W_c
         replay.update_in_graph = update_in_graph
         replay.metered = metered
         replay.static = static
@@ -847,7 +1065,11 @@ class Trainer:
 
     def capture_double(self, batch_a, batch_b, **kw):
         """Two captured steps over two sets of static input buffers (``DoubleBufferedStep``): the next batch is
-        loaded into the idle set on an input stream WHILE the current step runs."""
+        loaded into the idle set on an input stream WHILE the current step runs.  Not available with
+        ``accumulate`` > 1 (it would need two sets per role)."""
+        if self._accumulate > 1:
+            raise RuntimeError("capture_double is not available with accumulate = %d > 1: use capture() per role "
+                               "or bucketed()" % self._accumulate)
         return DoubleBufferedStep(self, batch_a, batch_b, **kw)
 
     def bucketed(self, **kw):
@@ -1052,7 +1274,13 @@ class StepCache:
     serve one of them.  GT slots are bucketed (8 / 16 / 32 / 64) so that box counts do not multiply the
     graphs.  Graphs of the same cloud shape share one pipelined coordinate pre-pass (``_GeoPipe``).
     Captures are ``dry``: they leave parameters, optimizer state, BatchNorm statistics and the dropout
-    counter untouched, so the sequence of updates equals that of eager steps."""
+    counter untouched, so the sequence of updates equals that of eager steps.
+
+    With ``trainer.accumulate`` > 1 a call is one MICRO-step and the role it plays in its group ("accumulate" /
+    "last", ``Trainer.capture``) joins the key: ``max_graphs`` still counts shapes, so up to ``2 * max_graphs``
+    graphs live, and both graphs of a shape share its pre-pass pipeline.  A capture may fall in the middle of a
+    group; being dry it leaves the group's accumulated gradients as they were.  ``captures`` records
+    (shape key, role, micro) of every capture."""
 
     GT_BUCKETS = (8, 16, 32, 64)
 
@@ -1064,6 +1292,7 @@ class StepCache:
         self.pipes = {}                               # cloud shape -> _GeoPipe
         self.seen = collections.Counter()
         self.stats = dict(eager=0, replayed=0, captured=0, evicted=0)
+        self.captures = []                            # (shape key, role or None, trainer.micro) per capture
 
     @classmethod
     def gt_slots(cls, gt_boxes):
@@ -1089,33 +1318,45 @@ class StepCache:
         coordinate pre-pass then runs underneath this step if the next batch replays a graph of the
         same cloud shape)."""
         key = self.key(batch)
-        r = self.graphs.get(key)
+        tr = self.trainer
+        role = None
+        if tr.accumulate > 1:
+            role = "last" if tr.micro == tr.accumulate - 1 else "accumulate"
+        gkey = key if role is None else key + (role,)
+        r = self.graphs.get(gkey)
+        if r is not None and r.accumulate != tr.accumulate:
+            raise RuntimeError("StepCache holds graphs captured with accumulate = %d and the trainer now has "
+                               "accumulate = %d: build a new StepCache" % (r.accumulate, tr.accumulate))
         if r is None:
             self.seen[key] += 1
             if self.seen[key] < self.capture_on:
                 self.stats["eager"] += 1
                 return self.trainer.step(batch)
-            while len(self.graphs) >= self.max_graphs:
-                old, dead = self.graphs.popitem(last=False)
-                self.stats["evicted"] += 1
-                # (the pipe - static index buffers + the pre-pass hipGraph - of a cloud shape survives while any
-                # graph of that shape does, INCLUDING the one about to be captured)
-                if old[0] != key[0] and not any(k[0] == old[0] for k in self.graphs):
-                    self.pipes.pop(old[0], None)
-                head = getattr(self.trainer.model, "pts_bbox_head", None)
-                if head is not None and hasattr(head, "unpin_metas"):
-                    head.unpin_metas(dead.static["img_metas"])
-                del dead
+            # (room is counted in SHAPES: the graphs of the other role of this shape do not count against it)
+            while key not in {k[:3] for k in self.graphs} and len({k[:3] for k in self.graphs}) >= self.max_graphs:
+                oldest = next(iter(self.graphs))[:3]
+                for old in [k for k in self.graphs if k[:3] == oldest]:
+                    dead = self.graphs.pop(old)
+                    self.stats["evicted"] += 1
+                    # (the pipe - static index buffers + the pre-pass hipGraph - of a cloud shape survives while any
+                    # graph of that shape does, INCLUDING the one about to be captured)
+                    if old[0] != key[0] and not any(k[0] == old[0] for k in self.graphs):
+                        self.pipes.pop(old[0], None)
+                    head = getattr(self.trainer.model, "pts_bbox_head", None)
+                    if head is not None and hasattr(head, "unpin_metas"):
+                        head.unpin_metas(dead.static["img_metas"])
+                    del dead
             pipe = self.pipes.get(key[0]) if self.prefetch else None
+            self.captures.append((key, role, tr.micro))
             r = self.trainer.capture(batch, warmup=self.warmup, prefetch_geometry=self.prefetch,
                                      max_gt=key[2] if isinstance(batch["gt_bboxes_3d"], (list, tuple)) else None,
-                                     dry=True, geo_pipe=pipe)
+                                     dry=True, geo_pipe=pipe, role=role)
             if self.prefetch and r.geo is not None:
                 self.pipes[key[0]] = r.geo
-            self.graphs[key] = r
+            self.graphs[gkey] = r
             self.stats["captured"] += 1
         else:
-            self.graphs.move_to_end(key)
+            self.graphs.move_to_end(gkey)
         r.load(batch)
         self.stats["replayed"] += 1
         if next_points is not None and tuple(next_points.shape) != key[0]:

@@ -2294,3 +2294,19 @@ def step_meter(scalars, opt_state, grad_scale, max_norm, ring):
     tab = (ctypes.c_void_p * len(scalars))(*[s.data_ptr() for s in scalars])
     _ffi.call("demf_step_meter", len(scalars), ctypes.addressof(tab), _p(opt_state), float(grad_scale),
               float(max_norm), _p(ring), int(ring.shape[0]), _stream())
+
+
+def scalars_accum(scalars, acc, scale):
+    """acc[i] += scale * scalars[i] for up to 10 single-element fp32 device tensors (views at any offset), one
+    launch (demf_scalars_accum, csrc/accum.hip): the loss terms of one micro-step of a gradient-accumulation group
+    into the accumulator the step meter reads at the group's last micro-step (scale = 1 / accumulate)."""
+    if not 1 <= len(scalars) <= METER_MAX_SCALARS:
+        raise ValueError("scalars_accum takes 1..%d scalars, got %d" % (METER_MAX_SCALARS, len(scalars)))
+    for s in scalars:
+        if not (isinstance(s, torch.Tensor) and s.is_cuda and s.dtype == torch.float32 and s.numel() == 1):
+            raise TypeError("scalars_accum: every scalar must be a single-element fp32 GPU tensor")
+    _chk(acc, "acc", torch.float32)
+    if acc.numel() < len(scalars):
+        raise ValueError("scalars_accum: the accumulator holds %d floats, %d scalars given" % (acc.numel(), len(scalars)))
+    tab = (ctypes.c_void_p * len(scalars))(*[s.data_ptr() for s in scalars])
+    _ffi.call("demf_scalars_accum", len(scalars), ctypes.addressof(tab), _p(acc), float(scale), _stream())

@@ -3,6 +3,7 @@
   python -m demf_amd.train --data-root R --ann-file sunrgbd_infos_train.pkl --work-dir W
                            [--val-ann-file sunrgbd_infos_val.pkl] [--load-from C] [--resume-from C] [--no-validate]
                            [--no-graphs] [--batch-size 16] [--epochs 36] [--seed 0] [--workers 4] [--log-interval 50]
+                           [--accumulate 1] [--autoscale-lr]
 
 ``fit`` feeds a dataset through ``SceneLoader(mode="train")``, the frozen image stream and ``engine.Trainer`` (one
 captured hipGraph per batch shape, ``StepCache``).  Losses, gradient norm and learning rate are logged through the
@@ -11,7 +12,9 @@ never waits for the GPU between log points.  Checkpoints are written per epoch, 
 a layout ``infer.load_checkpoint`` and the reference's tools read; ``resume_from`` continues with the next epoch
 (mmcv's resume granularity).  Validation is ``infer.run_test`` + ``dataset.evaluate``.
 
-Single process, one GPU.  Multi-rank training (the reference's tools/dist_train.sh) is not part of this module.
+Single process, one GPU.  Multi-rank training (the reference's tools/dist_train.sh) is not part of this module;
+``--accumulate 8`` forms the step of its 8 ranks x 16 scenes from 8 forward + backward passes instead (gradient
+accumulation, ``engine.Trainer(accumulate=W)``): iterations, log lines and the meter then count OPTIMIZER steps.
 """
 import argparse
 import functools
@@ -41,7 +44,9 @@ DEFAULTS = dict(
     log_interval=50,         # configs/_base_/default_runtime.py:6-7  log_config interval=50
     eval_interval=36,        # configs/demf/demf_votenet.py:275-278  evaluation interval=36
     seed=0,
+    accumulate=1,            # (tools/dist_train.sh:4 trains on 8 GPUs: --accumulate 8 is that step on one)
 )
+REFERENCE_WORLD = 8          # train.py:51-53: --autoscale-lr scales lr by len(gpu_ids) / 8
 
 
 def lr_factor(epoch, lr_steps=DEFAULTS["lr_steps"], gamma=DEFAULTS["gamma"]):
@@ -56,6 +61,32 @@ def loader_epoch(epoch, rep, repeat):
     if not 0 <= rep < repeat:
         raise ValueError(f"pass {rep} of {repeat}")
     return int(epoch) * int(repeat) + int(rep)
+
+
+def accumulation_plan(batches_per_pass, repeat, accumulate):
+    """One runner epoch is ``repeat`` passes of ``batches_per_pass`` batches; groups of ``accumulate`` batches run
+    across the passes and a group left incomplete at the end of the epoch is abandoned.
+    -> (optimizer steps per runner epoch, batches discarded at its end)."""
+    if batches_per_pass < 0 or repeat < 1 or accumulate < 1:
+        raise ValueError("accumulation_plan: batches_per_pass >= 0, repeat >= 1 and accumulate >= 1")
+    total = int(batches_per_pass) * int(repeat)
+    return total // int(accumulate), total % int(accumulate)
+
+
+def check_resume_accumulate(meta, accumulate, path="the checkpoint"):
+    """A resumed run keeps the checkpoint's ``accumulate`` (its ``iter`` and the meter's ``t`` count optimizer steps
+    of that size); a file written before the field existed reads as 1."""
+    was = int(meta.get("accumulate", 1))
+    if was != int(accumulate):
+        raise ValueError("resume_from %s was trained with accumulate = %d, this run asks for accumulate = %d"
+                         % (path, was, int(accumulate)))
+    return was
+
+
+def autoscale_lr(lr, accumulate=1, world=1):
+    """The reference's ``--autoscale-lr`` (train.py:51-53: lr x len(gpu_ids) / 8, the linear scaling rule) with the
+    number of 16-scene batches per optimizer step in the place of the GPU count: lr x (accumulate x world) / 8."""
+    return float(lr) * (int(accumulate) * int(world)) / REFERENCE_WORLD
 
 
 def format_log(rows, epoch, it, base_lr, seconds_per_iter, names=None):
@@ -191,19 +222,27 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
         ckpt_interval=DEFAULTS["ckpt_interval"], max_keep_ckpts=DEFAULTS["max_keep_ckpts"],
         eval_interval=DEFAULTS["eval_interval"], seed=DEFAULTS["seed"], workers=DEFAULTS["workers"], graphs=True,
         resume_from=None, load_from=None, num_points=20000, img_scale=(1333, 800), on_step=None, echo=True,
-        val_batch_size=None):
+        val_batch_size=None, accumulate=DEFAULTS["accumulate"]):
     """Train ``model`` (a ``DeMFVoteNet``: frozen image stream + hot path) on ``train_set`` for ``max_epochs`` runner
     epochs of ``repeat`` passes each.  -> dict(trainer, meter, stepper, epoch, iter, val).
 
-    ``on_step(info)``: called after every step has been enqueued, ``info = dict(epoch, iter, indices, loss)`` with
-    the 1-based epoch and global iteration, the batch's dataset indices and the step's loss as a DEVICE tensor
-    (reading it synchronises; the loop itself does not)."""
+    ``on_step(info)``: called after every micro-step has been enqueued, ``info = dict(epoch, iter, indices, loss,
+    micro)`` with the 1-based epoch and global iteration, the batch's dataset indices, the batch's loss as a DEVICE
+    tensor (reading it synchronises; the loop itself does not) and the micro-step's position in its group.
+
+    ``accumulate`` = W > 1: every optimizer step is formed from W consecutive batches (``engine.Trainer``);
+    ``iter``, the meter's ``t``, ``log_interval`` and the log lines count optimizer steps, groups run across the
+    ``repeat`` passes of a runner epoch, and the fewer than W batches left over at its end are abandoned
+    (``accumulation_plan``; the epoch's last log line carries ``discarded``), so that checkpoints, learning-rate
+    changes and validation fall on step boundaries."""
     from . import engine, infer
     from .meter import StepMeter, loss_names
     from .modules import DeMFHotPath
     from .pipeline import SceneLoader
     if batch_size < 1 or max_epochs < 0 or repeat < 1 or log_interval < 1 or ckpt_interval < 1 or eval_interval < 1:
         raise ValueError("batch_size, repeat, log_interval, ckpt_interval and eval_interval must be positive")
+    if isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1:
+        raise ValueError("accumulate must be a positive integer, got %r" % (accumulate,))
     if not hasattr(model, "extract_img_feat"):
         raise TypeError("fit() trains a detector with an image stream (DeMFVoteNet): the loader yields images")
     os.makedirs(work_dir, exist_ok=True)
@@ -218,18 +257,20 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
                   flush=True)
     # the runner computes the frozen image features itself and drives the hot path's forward_train
     trainer = engine.Trainer(model, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
-                             forward=functools.partial(DeMFHotPath.forward_train, model))
+                             forward=functools.partial(DeMFHotPath.forward_train, model), accumulate=accumulate)
     names = loss_names()
     meter = StepMeter(names, ring_rows=max(128, 2 * log_interval))
     trainer.attach_meter(meter)
     epoch0, it = 0, 0
     if resume_from is not None:
-        meta = restore_checkpoint(load_checkpoint_file(resume_from), model, trainer, meter)
+        ckpt = load_checkpoint_file(resume_from)
+        check_resume_accumulate(ckpt["meta"], accumulate, resume_from)
+        meta = restore_checkpoint(ckpt, model, trainer, meter)
         epoch0, it = int(meta["epoch"]), int(meta["iter"])
     stepper = trainer.bucketed() if graphs else None
     loader = SceneLoader(train_set, batch_size, "train", seed=seed, img_scale=img_scale, num_points=num_points,
                          workers=workers)
-    ipe = repeat * len(loader)                    # iterations per runner epoch
+    ipe, dropped = accumulation_plan(len(loader), repeat, accumulate)      # iterations per runner epoch
     log = _Log(os.path.join(work_dir, "train.log.json"), echo)
     rows, marks = [], []                          # meter rows not logged yet; (last t, epoch, iter, s/iter) per interval
 
@@ -238,9 +279,9 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
         check_finite(got, ipe)
         rows.extend(got)
         while marks and rows and rows[-1]["t"] >= marks[0][0]:
-            last_t, e, i, dt = marks.pop(0)
+            last_t, e, i, dt, extra = marks.pop(0)
             k = sum(1 for r in rows if r["t"] <= last_t)
-            log.write(format_log(rows[:k], e, i, lr, dt, names))
+            log.write(dict(format_log(rows[:k], e, i, lr, dt, names), **extra))
             del rows[:k]
 
     val = None
@@ -248,12 +289,15 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
         for epoch in range(epoch0, max_epochs):
             trainer.set_epoch(epoch, lr_steps, gamma)
             since, t_mark = 0, time.perf_counter()
+            it_end = it + ipe                     # the epoch's last optimizer step
 
             def mark():
                 nonlocal since, t_mark
                 now = time.perf_counter()
                 meter.snapshot()
-                marks.append((it - 1, epoch + 1, it, (now - t_mark) / since))
+                # (with accumulate > 1 the epoch's last line says how many batches its open group loses)
+                extra = dict(discarded=dropped) if accumulate > 1 and it == it_end else {}
+                marks.append((it - 1, epoch + 1, it, (now - t_mark) / since, extra))
                 since, t_mark = 0, now
 
             for rep in range(repeat):
@@ -262,17 +306,23 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
                     feats = model.extract_img_feat(batch["img"], batch["img_metas"])
                     step_batch = dict(points=batch["points"], img_features=feats, img_metas=batch["img_metas"],
                                       gt_bboxes_3d=batch["gt_bboxes_3d"], gt_labels_3d=batch["gt_labels_3d"])
+                    micro = trainer.micro
                     if stepper is not None:
                         loss = stepper.step(step_batch, next_points=None if nxt is None else nxt["points"])
                     else:
                         loss = trainer.step(step_batch)
-                    it += 1
-                    since += 1
+                    stepped = trainer.micro == 0  # (the group's last micro-step: an optimizer step has been enqueued)
                     if on_step is not None:
-                        on_step(dict(epoch=epoch + 1, iter=it, indices=tuple(batch.indices), loss=loss))
-                    if since >= log_interval:
-                        mark()
+                        on_step(dict(epoch=epoch + 1, iter=it + 1, indices=tuple(batch.indices), loss=loss,
+                                     micro=micro))
+                    if stepped:
+                        it += 1
+                        since += 1
+                        if since >= log_interval:
+                            mark()
                     drain(False)
+            if trainer.micro:
+                trainer.reset_accumulation()      # the epoch's incomplete group (``dropped`` batches) is abandoned
             if since:
                 mark()                            # the tail of the epoch
             drain(True)
@@ -280,7 +330,7 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
             if done % ckpt_interval == 0 or done == max_epochs:
                 meta = dict(epoch=done, iter=it, seed=int(seed), repeat=int(repeat), batch_size=int(batch_size),
                             lr=float(lr), lr_steps=[int(s) for s in lr_steps], gamma=float(gamma),
-                            max_epochs=int(max_epochs))
+                            max_epochs=int(max_epochs), accumulate=int(accumulate))
                 save_checkpoint(work_dir, done, make_checkpoint(model, trainer, meter, meta), max_keep_ckpts)
             if val_set is not None and (done % eval_interval == 0 or done == max_epochs):
                 trainer.flush()
@@ -307,9 +357,13 @@ def parse_args(argv=None):
     p.add_argument("--seed", type=int, default=DEFAULTS["seed"])
     p.add_argument("--workers", type=int, default=DEFAULTS["workers"])
     p.add_argument("--log-interval", type=int, default=DEFAULTS["log_interval"])
+    p.add_argument("--accumulate", type=int, default=DEFAULTS["accumulate"],
+                   help="batches per optimizer step (8: the reference's 8-GPU step on one GPU)")
+    p.add_argument("--autoscale-lr", action="store_true",
+                   help="the reference's linear scaling rule: lr x accumulate / 8")
     args = p.parse_args(argv)
-    if args.batch_size < 1 or args.workers < 1 or args.log_interval < 1:
-        p.error("--batch-size, --workers and --log-interval must be positive")
+    if args.batch_size < 1 or args.workers < 1 or args.log_interval < 1 or args.accumulate < 1:
+        p.error("--batch-size, --workers, --log-interval and --accumulate must be positive")
     if args.epochs < 0:
         p.error("--epochs must not be negative")
     if args.load_from and args.resume_from:
@@ -331,7 +385,9 @@ def main(argv=None, model=None, **fit_kwargs):
         model = DeMFVoteNet()
     kw = dict(val_set=val_set, batch_size=args.batch_size, max_epochs=args.epochs, seed=args.seed,
               workers=args.workers, log_interval=args.log_interval, graphs=not args.no_graphs,
-              resume_from=args.resume_from, load_from=args.load_from)
+              resume_from=args.resume_from, load_from=args.load_from, accumulate=args.accumulate)
+    if args.autoscale_lr:
+        kw["lr"] = autoscale_lr(DEFAULTS["lr"], args.accumulate)
     kw.update(fit_kwargs)
     return fit(model, train_set, args.work_dir, **kw)
 

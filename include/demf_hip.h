@@ -914,6 +914,29 @@ DEMF_INTERNAL int demf_adamw_state_f32(int nseg, const long long* seg_start, con
 DEMF_INTERNAL int demf_step_meter(int n, const float* const* scalars, const void* opt_state, float grad_scale,
                     float max_norm, void* ring, int rows, demf_stream_t stream);
 
+/* Gradient accumulation (csrc/accum.hip): W forward + backward passes feed ONE optimizer step, the reference's
+ * 8-rank step (tools/dist_train.sh:4) on one GPU.  The flat gradient buffer is zero between optimizer steps; every
+ * pass ADDS its gradients into it, the last pass takes the norm of the sum on its way, and demf_adamw_state_f32
+ * gets grad_scale = 1 / (W * world).
+ * demf_multi_add: the table, launch geometry and vector / scalar paths of demf_multi_copy (3 x n int64 DEVICE table
+ *   src | dst | words, grid (blocks_per_segment, n), 256 threads, 16-byte loads and stores with a 4q tail when
+ *   source and destination both sit on 16 bytes), computing dst[j] = dst[j] + src[j] in fp32 (one correctly rounded
+ *   add).  A null source adds nothing: dst is NOT written (demf_multi_copy zero-fills there).  n <= 65535.
+ * demf_multi_add_sumsq: the same, plus the sum of squares of every STORED sum added to opt_state.sumsq as
+ *   demf_multi_copy_sumsq adds it (fp32 partial per thread, fp64 wave / workgroup reduction, one fp64 atomic per
+ *   workgroup, none when the partial is 0).  A null-source segment is read and its squares counted: sumsq is the
+ *   squared norm of the whole accumulated buffer the table covers, not of this pass's share.
+ * demf_scalars_accum: acc[i] = acc[i] + scale * *scalars[i] for i < n (1..DEMF_METER_MAX_SCALARS), one wave, plain
+ *   stores, no atomics; scalars as demf_step_meter takes them (HOST array of DEVICE pointers, passed by value in
+ *   the kernel arguments), acc = n contiguous DEVICE floats.  NOT contracted: the product is rounded to fp32, then
+ *   the sum is (no fmaf; the library is built with -ffp-contract=off).  With scale = 1/W over the W passes of a
+ *   group, acc holds the group's mean loss terms, which demf_step_meter then reads as its scalars.          */
+DEMF_INTERNAL int demf_multi_add(int n, const void* table, int blocks_per_segment, demf_stream_t stream);
+DEMF_INTERNAL int demf_multi_add_sumsq(int n, const void* table, int blocks_per_segment, void* opt_state,
+                         demf_stream_t stream);
+DEMF_INTERNAL int demf_scalars_accum(int n, const float* const* scalars, float* acc, float scale,
+                       demf_stream_t stream);
+
 /* ------------------------------------------------------------------ *
  * Dense blocks of the DeMF fusion decoder layer (csrc/dense.hip)
  * Reference: demf/modeling/layers/transformer.py:55-80 -> mmcv DetrTransformerDecoderLayer
