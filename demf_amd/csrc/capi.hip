@@ -15,6 +15,9 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+static thread_local int g_last_form = DEMF_FORM_NONE;
+void set_last_form(int form) { g_last_form = form; }
+
 int check_launch(const char* what) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -28,6 +31,7 @@ int check_launch(const char* what) {
 
 extern "C" int demf_version(void) { return DEMF_ABI_VERSION; }
 extern "C" const char* demf_last_error(void) { return demf::g_err; }
+extern "C" int demf_mlp_last_form(void) { return demf::g_last_form; }
 
 // A HIP stream restricted to a subset of the CUs (hipExtStreamCreateWithCUMask).  Used by the
 // training engine to pin the latency-bound FPS pre-pass of the next batch to a few CUs and keep

@@ -11,6 +11,7 @@ namespace demf {
 // ---- error plumbing (thread-local text, C ABI return codes) --------------
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+void set_last_form(int form);   // DEMF_FORM_*: what demf_mlp_last_form() reports for this thread (csrc/capi.hip)
 
 #define DEMF_REQUIRE(cond, ...)             \
   do {                                      \

@@ -2687,6 +2687,7 @@ static int launch_gemm_t(const MlpArgs& a, hipStream_t s) {
       if constexpr (BF16 == 2) { if (f16_terms()) PCGO(3); else PCGO(2); }
       else PCGO(BF16);
 #undef PCGO
+      set_last_form(DEMF_FORM_PC);
       return check_launch("mlp_fwd_pc");
     }
     // weight-resident, barrier-free forward (mlp_fwd_res_kernel): 64-channel inputs, N = 64 / 128
@@ -2750,6 +2751,7 @@ static int launch_gemm_t(const MlpArgs& a, hipStream_t s) {
       }
 #undef FRGO
 #undef FRGO_
+      set_last_form(DEMF_FORM_RES);
       return check_launch("mlp_fwd_res");
     }
   }
@@ -2769,7 +2771,7 @@ static int launch_gemm_t(const MlpArgs& a, hipStream_t s) {
         (!RED || (a.fY && a.fss && a.fmi && a.stats))) {
       constexpr int P = BF16 == 2 ? 3 : 1;
       const int rc = launch_dx_tile<P, SP, RED>(a, s);
-      if (rc != -1000) return rc;
+      if (rc != -1000) { set_last_form(DEMF_FORM_TILE); return rc; }
     }
   }
   if constexpr ((BF16 == 1 || BF16 == 2) && !RED && !POOL && STATS && (PRO == PRO_BNRELU || PRO == PRO_NONE)) {
@@ -2783,9 +2785,10 @@ static int launch_gemm_t(const MlpArgs& a, hipStream_t s) {
         ((uintptr_t)a.X % 16 == 0) && ((uintptr_t)a.Bt % 16 == 0) && (PRO == PRO_NONE || a.vec != nullptr)) {
       constexpr int P = BF16 == 2 ? 3 : 1;
       const int rc = launch_fwd_tile<P, PRO == PRO_BNRELU>(a, s);
-      if (rc != -1000) return rc;
+      if (rc != -1000) { set_last_form(DEMF_FORM_TILE); return rc; }
     }
   }
+  set_last_form(DEMF_FORM_GENERIC);
   const dim3 block(256);
   // Two 32-row tiles per wave (256-row block tiles) while the accumulators + the raw prefetch fit
   // in 256 VGPRs: up to 4 column tiles for the forward prologues, up to 2 for the backward ones

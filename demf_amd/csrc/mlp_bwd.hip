@@ -31,6 +31,7 @@
 // Algorithmic HBM bytes per row: 4*(N [Y_l] + N [G, dense only] + K [Y_{l-1}] + K [dX, RED only]).
 #include "common.h"
 #include "bn_fin.h"
+#include "wide_map.h"
 
 namespace demf {
 
@@ -61,6 +62,10 @@ struct FusedBwdArgs {
   int ldk, ldw, fld, fc0;
   const float* W0;    // FIRST with ST bit 2: (K x 4) weight of layer 0 - Y_0 = fX.W0^T is recomputed, Xp is not read
   int dbg;            // DEMF_BWD_DBG (timing experiments, results wrong): bit 0 = the dW flush is skipped
+  // WIDE (demf_mlp_bwd_fused_wide): ONE launch over nchunk column chunks of K channels each (fld = nchunk * K).  The
+  // pointers are the whole layer's (fc0 = 0); a workgroup derives its chunk and its slab sequence from its block id
+  // (csrc/wide_map.h) and offsets Xp, dX, W, dW and the column base itself.
+  int nchunk;
 };
 
 // one fp32 value -> P bf16 planes: P = 1: rounded; P = 3: x = h + m + l exactly (csrc/mlp.hip, mode 2)
@@ -167,8 +172,10 @@ __device__ __forceinline__ auto load_row(const float* __restrict__ base, size_t 
 // 4-wave workgroups run two per CU.  Wave w -> nt = w % NTN, kg = w / NTN.
 // ST (bf16 compute mode, BASELINE configs[3]): rows stored as bf16 in HBM - bit 0: Y_{l-1} (Xp), bit 1:
 // Y_l, the dense upstream gradient G and the input gradient dX this launch writes.
-template <int NTN, int KT, int KG, bool SPARSE, int CM, int EPI, int ST = 0>   // CM 1 bf16 / 2 three-term ; EPI 0 RED / 1 FIRST
+// WIDE: the launch covers every K-channel chunk of a wider layer l-1 (FusedBwdArgs::nchunk); chunk-mates on one XCD.
+template <int NTN, int KT, int KG, bool SPARSE, int CM, int EPI, int ST = 0, bool WIDE = false>   // CM 1 bf16 / 2 three-term ; EPI 0 RED / 1 FIRST
 __global__ __launch_bounds__(64 * NTN * KG, 512 / (64 * NTN * KG)) void mlp_bwd_fused_kernel(FusedBwdArgs p) {
+  static_assert(!WIDE || (EPI == 0 && ST == 0), "WIDE: RED epilogue, fp32 rows");
   constexpr bool XB = (ST & 1) != 0, YB = (ST & 2) != 0;
   // ST bit 2 (FIRST only): layer 0's raw output is not stored - its 4-float input rows fX and its (K x 4) weight
   // W0 rebuild the values this kernel needs (two channels of four rows per lane for the staged activation,
@@ -212,10 +219,23 @@ __global__ __launch_bounds__(64 * NTN * KG, 512 / (64 * NTN * KG)) void mlp_bwd_
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // provably wave-uniform: scalar branches below
   const int lr = lane & 31, lh = lane >> 5;
   const int nt = wave % NTN, kg = wave / NTN;     // dW: channel slice nt, K tiles kg*KTW ..
+  // this workgroup's columns of layer l-1 and its slab sequence (all wave-uniform)
+  // (WIDE only; the other forms read the launch's arguments as before.  Scalar registers, and the offset is added
+  // where a pointer is used: the (8, 4, 1) forms sit at the VGPR ceiling)
+  int w_fc0 = 0, w_slab0 = 0, w_step = 0;
+  if constexpr (WIDE) {
+    const WideBlock wb = wide_block((int)blockIdx.x, p.nchunk, (int)gridDim.x / p.nchunk);
+    w_fc0 = __builtin_amdgcn_readfirstlane(wb.chunk * (KT * 32));
+    w_slab0 = __builtin_amdgcn_readfirstlane(wb.first);
+    w_step = __builtin_amdgcn_readfirstlane(wb.stride);
+  }
+#define FB_FC0 (WIDE ? w_fc0 : p.fc0)
+#define FB_STEP (WIDE ? w_step : (int)gridDim.x)
+#define FB_PTR(ptr) (WIDE ? (ptr) + w_fc0 : (ptr))
   const int dkt = wave % KT, dnh = wave / KT;     // dX: K tile dkt, channel slices dnh*SL ..
   for (int i = tid; i < 5 * N; i += NT) s_vy[i] = p.vec[i];
   for (int i = tid; i < 2 * K; i += NT) {
-    const int g = (i < K ? i : p.fld + i - K) + p.fc0;           // [scale | shift], [mean | invstd] of the chunk
+    const int g = (i < K ? i : p.fld + i - K) + FB_FC0;           // [scale | shift], [mean | invstd] of the chunk
     s_px[i] = p.pss[g];
     s_px[2 * K + i] = p.pmi[g];
   }
@@ -236,7 +256,7 @@ __global__ __launch_bounds__(64 * NTN * KG, 512 / (64 * NTN * KG)) void mlp_bwd_
       __bf16 t[8][P];
 #pragma unroll
       for (int e = 0; e < 8; ++e)
-        split_planes<P>(p.W[(size_t)(32 * (dnh * SL + sl) + 16 * s + 8 * lh + e) * p.ldw + 32 * dkt + lr], t[e]);
+        split_planes<P>(FB_PTR(p.W)[(size_t)(32 * (dnh * SL + sl) + 16 * s + 8 * lh + e) * p.ldw + 32 * dkt + lr], t[e]);
 #pragma unroll
       for (int q = 0; q < P; ++q)
 #pragma unroll
@@ -288,7 +308,7 @@ __global__ __launch_bounds__(64 * NTN * KG, 512 / (64 * NTN * KG)) void mlp_bwd_
       if constexpr (XR) {
         rq[j] = *reinterpret_cast<const float4*>(p.fX + (size_t)xrow * 4);      // rebuilt in the transform
       } else {
-        const auto xv = load_row<2, XB>(p.Xp, (size_t)xrow * p.ldk + 2 * x_c2);
+        const auto xv = load_row<2, XB>(FB_PTR(p.Xp), (size_t)xrow * p.ldk + 2 * x_c2);
         rx[j] = make_float2(xv[0], xv[1]);
       }
     }
@@ -303,7 +323,7 @@ __global__ __launch_bounds__(64 * NTN * KG, 512 / (64 * NTN * KG)) void mlp_bwd_
   };
 
   const int nslab = (p.R + RS - 1) / RS;
-  int slab = blockIdx.x;
+  int slab = WIDE ? w_slab0 : (int)blockIdx.x;
   constexpr bool PREF = !(NTN == 8 && P == 3);   // (256,128) three-term: no registers to hold a slab ahead
   if (PREF && slab < nslab) fetch(slab);
   // (measured: staggering the start of the second workgroup per CU by 0.5 ... 4 k cycles changes nothing)
@@ -351,7 +371,7 @@ __global__ __launch_bounds__(64 * NTN * KG, 512 / (64 * NTN * KG)) void mlp_bwd_
   }
   __syncthreads();
 
-  for (; slab < nslab; slab += gridDim.x) {
+  for (; slab < nslab; slab += FB_STEP) {
     const int row0 = slab * RS;
     if constexpr (!PREF) fetch(slab);
     // ---- [A] dY = gi*dZ + a*y + b on the lane's patch, split once, both orientations into LDS -------
@@ -452,7 +472,7 @@ __global__ __launch_bounds__(64 * NTN * KG, 512 / (64 * NTN * KG)) void mlp_bwd_
       }
     }
     // ---- [B] next slab's rows in flight underneath the MFMA phase ----------------------------------
-    if (PREF && slab + (int)gridDim.x < nslab) fetch(slab + (int)gridDim.x);
+    if (PREF && slab + FB_STEP < nslab) fetch(slab + FB_STEP);
     lds_barrier();        // planes of every wave in place; the last epilogue is done with the dX tile
     // ---- [C] dW += dY^T.act(Y_{l-1}); dX partial over this wave's channel slice ----------------------
     f32x16 pa;
@@ -490,7 +510,7 @@ __global__ __launch_bounds__(64 * NTN * KG, 512 / (64 * NTN * KG)) void mlp_bwd_
     }
     if constexpr (H2) {
       // the next slab's rows have arrived underneath the MFMA phase: its maximum, in front of the fold barriers
-      if (slab + (int)gridDim.x < nslab) publish_max((slab + (int)gridDim.x) * RS, par);
+      if (slab + FB_STEP < nslab) publish_max((slab + FB_STEP) * RS, par);
     }
     // The NH partial tiles of a K tile meet in the fp32 LDS tile in NH ordered rounds: in round j wave
     // (dkt, dnh) owns row chunk (dnh + j) % NH (32/NH rows = CR accumulator registers) - the first round
@@ -540,7 +560,7 @@ __global__ __launch_bounds__(64 * NTN * KG, 512 / (64 * NTN * KG)) void mlp_bwd_
             y.z = __builtin_fmaf(r.w, w4[2].w, __builtin_fmaf(r.z, w4[2].z, __builtin_fmaf(r.y, w4[2].y, r.x * w4[2].x)));
             y.w = __builtin_fmaf(r.w, w4[3].w, __builtin_fmaf(r.z, w4[3].z, __builtin_fmaf(r.y, w4[3].y, r.x * w4[3].x)));
           } else {
-            const auto yv = load_row<4, XB>(p.Xp, (size_t)row * p.ldk + 4 * e_cq);
+            const auto yv = load_row<4, XB>(FB_PTR(p.Xp), (size_t)row * p.ldk + 4 * e_cq);
             y = make_float4(yv[0], yv[1], yv[2], yv[3]);
           }
           float dz[4];
@@ -562,7 +582,7 @@ __global__ __launch_bounds__(64 * NTN * KG, 512 / (64 * NTN * KG)) void mlp_bwd_
               split_pair<1>(dx.z, dx.w, o1);
               *reinterpret_cast<uint2*>(reinterpret_cast<__bf16*>(p.dX) + (size_t)row * p.ldk + 4 * e_cq) = make_uint2(o0[0], o1[0]);
             } else {
-              *reinterpret_cast<float4*>(p.dX + (size_t)row * p.ldk + 4 * e_cq) = dx;
+              *reinterpret_cast<float4*>(FB_PTR(p.dX) + (size_t)row * p.ldk + 4 * e_cq) = dx;
             }
           } else {
             const float4 x = *reinterpret_cast<const float4*>(p.fX + (size_t)row * 4);
@@ -598,7 +618,7 @@ __global__ __launch_bounds__(64 * NTN * KG, 512 / (64 * NTN * KG)) void mlp_bwd_
       for (int r = 0; r < 16; ++r) {
         const int n = 32 * nt + (r & 3) + 8 * (r >> 2) + 4 * lh;
         const int k = 32 * (kg * KTW + kk) + lr;
-        atomicAdd(p.dW + (size_t)n * p.ldw + k, H2 ? dwacc[kk][r] * inv : dwacc[kk][r]);
+        atomicAdd(FB_PTR(p.dW) + (size_t)n * p.ldw + k, H2 ? dwacc[kk][r] * inv : dwacc[kk][r]);
       }
   }
   // column sums: lanes with the same float4 column inside a wave first, then the 8 waves through LDS
@@ -632,7 +652,7 @@ __global__ __launch_bounds__(64 * NTN * KG, 512 / (64 * NTN * KG)) void mlp_bwd_
     for (int w = 0; w < NW; ++w) t += s_red[(w * QK + cq) * NV + q];
     if (q < 8) {
       const int col = 4 * cq + (q & 3);
-      if constexpr (EPI == 0) atomicAdd(p.g12 + (q >> 2) * p.fld + p.fc0 + col, (double)t);
+      if constexpr (EPI == 0) atomicAdd(p.g12 + (q >> 2) * p.fld + FB_FC0 + col, (double)t);
       else atomicAdd(p.fsum + (q >> 2) * K + col, (double)t);
     } else if (q < 40) {
       // FIRST: P (K x 4) at 2K, Q (K x 4) at 6K
@@ -648,9 +668,13 @@ __global__ __launch_bounds__(64 * NTN * KG, 512 / (64 * NTN * KG)) void mlp_bwd_
       sync_drained();
       if (tid == 0) s_last = last_workgroup(p.vfin.ticket, (int)gridDim.x, (int)blockIdx.x);
       __syncthreads();
-      if (s_last) bn_vec_finalize(p.vfin, p.fld, p.fc0, K, p.g12, tid, NT);
+      // (WIDE: one ticket for the launch - the last workgroup holds the sums of EVERY chunk)
+      if (s_last) bn_vec_finalize(p.vfin, p.fld, WIDE ? 0 : p.fc0, WIDE ? p.fld : K, p.g12, tid, NT);
     }
   }
+#undef FB_FC0
+#undef FB_STEP
+#undef FB_PTR
 }
 
 // ---- backward of a POOLED last layer without its output -------------------------------------------
@@ -1136,14 +1160,14 @@ static int vectors_without_ticket(const BnVecFin& vf, int K, double* g12, demf_s
   return demf_bn_bwd_vectors(K, (long long)vf.count, g12, vf.gamma, vf.ss, vf.mi, vf.vec, vf.dgamma, vf.dbeta, stream);
 }
 
-template <int NTN, int KT, int KG, bool SPARSE, int CM, int EPI, int ST = 0>
+template <int NTN, int KT, int KG, bool SPARSE, int CM, int EPI, int ST = 0, bool WIDE = false>
 static int launch_fused(const FusedBwdArgs& a, hipStream_t s) {
   constexpr int P = CM == 2 ? 3 : (CM == 3 ? 2 : 1);
   constexpr int N = NTN * 32, K = KT * 32, NW = NTN * KG;
   const size_t bytes = (size_t)NTN * P * 2 * 2048 + (size_t)P * K * 64 + sizeof(float) * (32 * K + 5 * N + 4 * K + 4 * K + 24);
   static bool configured = false;
   if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bwd_fused_kernel<NTN, KT, KG, SPARSE, CM, EPI, ST>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bwd_fused_kernel<NTN, KT, KG, SPARSE, CM, EPI, ST, WIDE>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
       set_error("mlp_bwd_fused: cannot reserve %zu bytes of LDS", bytes);
       return DEMF_ELAUNCH;
@@ -1161,8 +1185,10 @@ static int launch_fused(const FusedBwdArgs& a, hipStream_t s) {
     return v ? atoi(v) : 240;
   }();
   const int cap = cus * (8 / NW);
-  const int gx = nslab < cap ? nslab : cap;
-  hipLaunchKernelGGL((mlp_bwd_fused_kernel<NTN, KT, KG, SPARSE, CM, EPI, ST>), dim3(gx), dim3(64 * NW), bytes, s, a);
+  // WIDE: nchunk x (workgroups per chunk) - half as many workgroups per chunk as a launch per chunk would take, each
+  // walking twice the slabs: one weight-fragment load, one dW flush (cap / nchunk partials per element) and one drain
+  const int gx = WIDE ? a.nchunk * wide_members(nslab, a.nchunk, cap) : (nslab < cap ? nslab : cap);
+  hipLaunchKernelGGL((mlp_bwd_fused_kernel<NTN, KT, KG, SPARSE, CM, EPI, ST, WIDE>), dim3(gx), dim3(64 * NW), bytes, s, a);
   return check_launch("mlp_bwd_fused");
 }
 
@@ -1201,6 +1227,7 @@ extern "C" int demf_mlp_bwd_fused(int R, int N, int K, const float* G, const flo
   DEMF_REQUIRE(Y && vec6 && W && Yprev && scale_shift_prev && mean_invstd_prev && dW &&
                    (G || (dP && arg)) && (first ? (X0 != nullptr) : (dX && g12_prev)),
                "mlp_bwd_fused: null pointer");
+  set_last_form(DEMF_FORM_FUSED);
   FusedBwdArgs a{};
   { static const int dbg = getenv("DEMF_BWD_DBG") ? atoi(getenv("DEMF_BWD_DBG")) : 0; a.dbg = dbg; }
   a.R = R; a.N = N; a.K = K; a.ns = ns; a.Yl = Y; a.G = G; a.dP = dP; a.arg = arg; a.vec = vec6;
@@ -1257,6 +1284,7 @@ extern "C" int demf_mlp_bwd_fused_cols(int R, int N, int Ktot, int c0, int Kc, c
                R, N, Ktot, c0, Kc, ns, (int)sparse, compute_mode());
   DEMF_REQUIRE(Y && vec6 && W && Yprev && scale_shift_prev && mean_invstd_prev && dW && (G || (dP && arg)) && dX &&
                    g12_prev, "mlp_bwd_fused_cols: null pointer");
+  set_last_form(DEMF_FORM_FUSED_COLS);
   FusedBwdArgs a{};
   { static const int dbg = getenv("DEMF_BWD_DBG") ? atoi(getenv("DEMF_BWD_DBG")) : 0; a.dbg = dbg; }
   a.R = R; a.N = N; a.K = Kc; a.ns = ns; a.Yl = Y; a.G = G; a.dP = dP; a.arg = arg; a.vec = vec6;
@@ -1283,6 +1311,52 @@ extern "C" int demf_mlp_bwd_fused_cols(int R, int N, int Ktot, int c0, int Kc, c
   if (N == 256 && Kc == 128) { if (sparse) { FGO(8, 4, 1, true); } else { FGO(8, 4, 1, false); } }
   if (sparse) { FGO(2, 2, 2, true); } else { FGO(2, 2, 2, false); }
 #undef FGO
+}
+
+// One launch for ALL 128-column chunks of a wider layer l-1 (N = 256 outputs, Ktot = 256 / 384 / 512): the contract of
+// demf_mlp_bwd_fused_cols called for c0 = 0, 128, ..., on the same (8, 4, 1) kernel.  A launch per chunk pays the
+// per-launch costs - weight fragments loaded and split per workgroup, the dW flush of every workgroup's N x 128 partials,
+// the drain, the ticket tail - once per chunk on only ~4 slabs per workgroup at the vote aggregation's 32 768 rows,
+// which is why that form never beat the two-launch path (DESIGN_LOG round 7).  Here the grid is
+// nchunk x (cap / nchunk) workgroups (csrc/wide_map.h): each walks nchunk times as many slabs of ONE chunk, a dW
+// element receives cap / nchunk partials, chunk-mates on the same slabs share an XCD's L2, and there is one ticket:
+// the last workgroup of the launch forms the backward vectors of all Ktot channels.
+extern "C" int demf_mlp_bwd_fused_wide(int R, int N, int Ktot, const float* G, const float* dP, const int* arg, int ns,
+                                       const float* Y, const float* vec6, const float* W, const float* Yprev,
+                                       const float* scale_shift_prev, const float* mean_invstd_prev, float* dX,
+                                       float* dW, double* g12_prev, const float* gamma_prev, float* vec6_prev,
+                                       float* dgamma_prev, float* dbeta_prev, demf_stream_t stream) {
+  const bool sparse = G == nullptr;
+  constexpr int Kc = 128;
+  DEMF_REQUIRE(N == 256 && fused_supported(R, N, Kc, ns, sparse, 0) && Ktot > Kc && Ktot % Kc == 0 && Ktot <= 512,
+               "mlp_bwd_fused_wide: unsupported shape / mode R=%d N=%d Ktot=%d ns=%d sparse=%d mode=%d",
+               R, N, Ktot, ns, (int)sparse, compute_mode());
+  DEMF_REQUIRE(Y && vec6 && W && Yprev && scale_shift_prev && mean_invstd_prev && dW && (G || (dP && arg)) && dX &&
+                   g12_prev, "mlp_bwd_fused_wide: null pointer");
+  set_last_form(DEMF_FORM_FUSED_WIDE);
+  FusedBwdArgs a{};
+  { static const int dbg = getenv("DEMF_BWD_DBG") ? atoi(getenv("DEMF_BWD_DBG")) : 0; a.dbg = dbg; }
+  a.R = R; a.N = N; a.K = Kc; a.ns = ns; a.Yl = Y; a.G = G; a.dP = dP; a.arg = arg; a.vec = vec6;
+  a.Xp = Yprev; a.dX = dX; a.W = W; a.dW = dW;
+  a.pss = scale_shift_prev; a.pmi = mean_invstd_prev; a.g12 = g12_prev;
+  a.ldk = Ktot; a.ldw = Ktot; a.fld = Ktot; a.fc0 = 0; a.nchunk = Ktot / Kc;
+  if (gamma_prev != nullptr) {
+    DEMF_REQUIRE(vec6_prev && dgamma_prev && dbeta_prev, "mlp_bwd_fused_wide: vectors of layer l-1 need all three outputs");
+    a.vfin = BnVecFin{(double)R, gamma_prev, scale_shift_prev, mean_invstd_prev, vec6_prev, dgamma_prev,
+                      dbeta_prev, sched_slot()};
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int cm = compute_mode();
+  const bool h2 = f16_terms() && fused_h2_on();
+  int rc;
+  if (sparse) {
+    rc = cm == 1 ? launch_fused<8, 4, 1, true, 1, 0, 0, true>(a, s)
+                 : (h2 ? launch_fused<8, 4, 1, true, 3, 0, 0, true>(a, s) : launch_fused<8, 4, 1, true, 2, 0, 0, true>(a, s));
+  } else {
+    rc = cm == 1 ? launch_fused<8, 4, 1, false, 1, 0, 0, true>(a, s)
+                 : (h2 ? launch_fused<8, 4, 1, false, 3, 0, 0, true>(a, s) : launch_fused<8, 4, 1, false, 2, 0, 0, true>(a, s));
+  }
+  return rc ? rc : vectors_without_ticket(a.vfin, Ktot, g12_prev, stream);      // (DEMF_STATIC_TILES=1: no ticket)
 }
 
 static int pool_bwd_grid(int R) {
@@ -1318,6 +1392,7 @@ extern "C" int demf_mlp_bwd_pool(int R, int N, int K, int ns, const float* dP, c
                "mlp_bwd_pool: unsupported shape / mode R=%d N=%d K=%d ns=%d mode=%d", R, N, K, ns, cm);
   DEMF_REQUIRE(dP && arg && yraw && vec6 && W && Yprev && scale_shift_prev && mean_invstd_prev && dX && dW &&
                    g12_prev && workspace, "mlp_bwd_pool: null pointer");
+  set_last_form(DEMF_FORM_POOL);
   PoolBwdArgs a{};
   a.R = R; a.ns = ns; a.Xp = Yprev; a.pss = scale_shift_prev; a.pmi = mean_invstd_prev; a.W = W; a.vec = vec6;
   a.dP = dP; a.arg = arg; a.yraw = yraw; a.dX = dX; a.part = workspace; a.g12 = g12_prev;
@@ -1373,6 +1448,7 @@ extern "C" int demf_mlp_bwd_fused_x4(int R, int N, int K, const float* G, const 
                R, N, K, compute_mode());
   DEMF_REQUIRE(G && Y && vec6 && W && X0 && W0 && scale_shift_prev && mean_invstd_prev && dW && first_sums,
                "mlp_bwd_fused_x4: null pointer");
+  set_last_form(DEMF_FORM_FUSED);
   FusedBwdArgs a{};
   { static const int dbg = getenv("DEMF_BWD_DBG") ? atoi(getenv("DEMF_BWD_DBG")) : 0; a.dbg = dbg; }
   a.R = R; a.N = N; a.K = K; a.ns = 1; a.Yl = Y; a.G = G; a.vec = vec6; a.Xp = nullptr; a.pss = scale_shift_prev;

@@ -1088,6 +1088,21 @@ def _bwd_fused_cols_ok(R, N, K, ns, sparse):
     return N == 256 and K > 128 and K % 128 == 0 and K <= 512
 
 
+# rows from which such a layer takes the one-pass backward as ONE launch over all its 128-column chunks
+# (demf_mlp_bwd_fused_wide, csrc/mlp_bwd.hip); 0 = never.  DEMF_FUSED_COLS_MIN_R > 0 takes precedence (A/B).
+_FUSED_WIDE_MIN_R = int(os.environ.get("DEMF_FUSED_WIDE_MIN_R", "16384"))
+
+
+def _bwd_fused_wide_ok(R, N, K, ns, sparse):
+    """demf_mlp_bwd_fused_wide: a 256-output layer whose input has K = 256 / 384 / 512 channels (the vote
+    aggregation's layers 2 and 3), on enough rows to fill the persistent grid."""
+    if _NO_BWD_FUSE or _COMPUTE_MODE not in (1, 2) or _FUSED_WIDE_MIN_R <= 0 or R < _FUSED_WIDE_MIN_R:
+        return False
+    if sparse and (ns < 4 or ns % 4):
+        return False
+    return N == 256 and K in (256, 384, 512)
+
+
 # SA1's pooled last layer without its (R x 128) output: the forward does not store it, the backward is
 # written in terms of the layer's INPUT activations (csrc/mlp_bwd.hip mlp_bwd_pool_kernel).  A/B switch.
 _POOL_NOY = bool(int(os.environ.get("DEMF_POOL_NOY", "1")))
@@ -1528,6 +1543,28 @@ class _SharedMLPPool(Function):
                               _p(sss[l - 1]), _p(mis[l - 1]), _p(dX), _p(dW), _p(g12p),
                               _p(gammas[l - 1]) if (_VEC_FIN & 2) else None, _p(vec_ready[0]),
                               _p(vec_ready[1]), _p(vec_ready[2]), st)
+                if not (_VEC_FIN & 2):
+                    g12_pending = g12p
+                G = dX
+                continue
+            if l > 0 and ldx == K and not first_here and not s16 and _bwd_fused_wide_ok(R, N, K, ns, sparse):
+                # ... as ONE launch over all the column chunks: dX, dW, the sums and (last workgroup of the
+                # launch) the vectors of every channel of layer l-1
+                grads[7 * l], grads[7 * l + 1], grads[7 * l + 2] = dW, dgamma, dbeta
+                if ctx.bias_shapes[l] is not None:
+                    grads[7 * l + 5] = ws32[o32:o32 + N].view(ctx.bias_shapes[l])
+                    o32 += N
+                dX = torch.empty((R, K), dtype=torch.float32, device=dev)
+                g12p = ws64[o64:o64 + 2 * K]
+                o64 += 2 * K
+                vec_ready = (torch.empty(5 * K, dtype=torch.float32, device=dev),
+                             torch.empty(K, dtype=torch.float32, device=dev),
+                             torch.empty(K, dtype=torch.float32, device=dev))
+                _ffi.call("demf_mlp_bwd_fused_wide", R, N, K, _p(G), _p(dP if sparse else None),
+                          _p(arg if sparse else None), ns, _p(Ys[l]), _p(vec6), _p(W), _p(Ys[l - 1]),
+                          _p(sss[l - 1]), _p(mis[l - 1]), _p(dX), _p(dW), _p(g12p),
+                          _p(gammas[l - 1]) if (_VEC_FIN & 2) else None, _p(vec_ready[0]),
+                          _p(vec_ready[1]), _p(vec_ready[2]), st)
                 if not (_VEC_FIN & 2):
                     g12_pending = g12p
                 G = dX

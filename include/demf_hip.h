@@ -490,6 +490,31 @@ DEMF_INTERNAL int demf_mlp_bwd_fused_cols(int R, int N, int Ktot, int c0, int Kc
                             const float* mean_invstd_prev, float* dX, float* dW, double* g12_prev,
                             const float* gamma_prev, float* vec6_prev, float* dgamma_prev,
                             float* dbeta_prev, demf_stream_t stream);
+/* What demf_mlp_bwd_fused_cols called for every 128-column chunk (c0 = 0, 128, ...) does, in ONE launch: N = 256,
+ * Ktot in {256, 384, 512}.  A workgroup takes its chunk and its rows from its block id (csrc/wide_map.h): the
+ * workgroups that walk the same rows of different chunks share an XCD's L2, there are Ktot/128 times fewer
+ * workgroups (and dW partials) per chunk, and the launch's single last workgroup forms the backward vectors of all
+ * Ktot channels of layer l-1.  Same argument contract and compute modes as demf_mlp_bwd_fused_cols. */
+DEMF_INTERNAL int demf_mlp_bwd_fused_wide(int R, int N, int Ktot, const float* G, const float* dP, const int* arg, int ns,
+                            const float* Y, const float* vec6, const float* W, const float* Yprev,
+                            const float* scale_shift_prev, const float* mean_invstd_prev, float* dX,
+                            float* dW, double* g12_prev, const float* gamma_prev, float* vec6_prev,
+                            float* dgamma_prev, float* dbeta_prev, demf_stream_t stream);
+
+/* Which kernel form the last shared-MLP launch of THIS thread took - a host-side record (no device work) set by the
+ * forward / input-gradient dispatch of csrc/mlp.hip and by the one-pass backward entry points of csrc/mlp_bwd.hip.
+ * For tests: from Python a dispatch condition that silently stops matching is invisible, the same entry point just
+ * runs a slower kernel and every numeric check still passes. */
+#define DEMF_FORM_NONE 0        /* no such launch on this thread yet */
+#define DEMF_FORM_GENERIC 1     /* mlp_gemm_kernel (any prologue; also the pooled epilogue) */
+#define DEMF_FORM_TILE 2        /* mlp_fwd_tile_kernel / mlp_dx_tile_kernel (few rows) */
+#define DEMF_FORM_RES 3         /* mlp_fwd_res_kernel (weight-resident, 64-channel inputs) */
+#define DEMF_FORM_PC 4          /* mlp_fwd_pc_kernel (producer / consumer, 128-channel inputs) */
+#define DEMF_FORM_FUSED 5       /* mlp_bwd_fused_kernel through demf_mlp_bwd_fused / _x4 */
+#define DEMF_FORM_FUSED_COLS 6  /* ... through demf_mlp_bwd_fused_cols: one launch per column chunk */
+#define DEMF_FORM_FUSED_WIDE 7  /* ... through demf_mlp_bwd_fused_wide: one launch for all column chunks */
+#define DEMF_FORM_POOL 8        /* mlp_bwd_pool_kernel (demf_mlp_bwd_pool) */
+DEMF_INTERNAL int demf_mlp_last_form(void);
 
 /* SA1-shaped stacks (4-float grouped rows -> N0 <= 64 channels -> ...): the first layer WITHOUT its (R x N0)
  * output.  y = x.W0^T is linear in the 16-byte row, so
