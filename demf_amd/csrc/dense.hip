@@ -1274,8 +1274,9 @@ extern "C" int demf_gemm_group_f32(const demf_gemm_desc* descs, int n, demf_stre
   return DEMF_OK;
 }
 
+// (a width that is no multiple of 64 must not round down to a narrower kernel: wrong row pitch)
 #define LN_DISPATCH(C, CALL)                       \
-  switch ((C) / 64) {                              \
+  switch ((C) % 64 == 0 ? (C) / 64 : 0) {          \
     case 1: CALL(1); break;                        \
     case 2: CALL(2); break;                        \
     case 4: CALL(4); break;                        \
