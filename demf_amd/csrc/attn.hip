@@ -302,9 +302,8 @@ static int attn_check(int B, int H, int Q, int Dh) {
 }
 
 template <typename K>
-static int attn_lds(K kernel, const char* what) {
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)(AT_LDS_FLOATS * sizeof(float))) != hipSuccess) {
+static int attn_lds(K kernel, const char* what, unsigned long long* reserved) {
+  if (!reserve_lds(reinterpret_cast<const void*>(kernel), (int)(AT_LDS_FLOATS * sizeof(float)), reserved)) {
     set_error("%s: cannot reserve %zu bytes of LDS", what, AT_LDS_FLOATS * sizeof(float));
     return DEMF_ELAUNCH;
   }
@@ -325,12 +324,9 @@ extern "C" int demf_attn_core_fwd(int B, int H, int Q, int Dh, const float* qkv,
   AttnArgs a{};
   a.B = B; a.H = H; a.qkv = qkv; a.o = out; a.stats = stats; a.prob = prob; a.pdrop = prob_dropped;
   a.scale = scale; a.p = p; a.rng = (const unsigned long long*)rng; a.op = (unsigned)op_id;
-  static bool configured = false;
-  if (!configured) {
-    if (int e = attn_lds(&attn_fwd_kernel<false>, "attn_core_fwd")) return e;
-    if (int e = attn_lds(&attn_fwd_kernel<true>, "attn_core_fwd")) return e;
-    configured = true;
-  }
+  static unsigned long long reserved[2] = {0, 0};      // per kernel instantiation: bit per device
+  if (int e = attn_lds(&attn_fwd_kernel<false>, "attn_core_fwd", &reserved[0])) return e;
+  if (int e = attn_lds(&attn_fwd_kernel<true>, "attn_core_fwd", &reserved[1])) return e;
   const size_t bytes = AT_LDS_FLOATS * sizeof(float);
   if (compute_bf16()) hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3(B * H * 4), dim3(256), bytes, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(attn_fwd_kernel<false>, dim3(B * H * 4), dim3(256), bytes, (hipStream_t)stream, a);
@@ -347,12 +343,9 @@ extern "C" int demf_attn_core_bwd(int B, int H, int Q, int Dh, const float* qkv,
   AttnArgs a{};
   a.B = B; a.H = H; a.qkv = qkv; a.out = out; a.dout = dout; a.stats = const_cast<float*>(stats); a.dqkv = dqkv;
   a.scale = scale; a.p = p; a.rng = (const unsigned long long*)rng; a.op = (unsigned)op_id;
-  static bool configured = false;
-  if (!configured) {
-    if (int e = attn_lds(&attn_bwd_kernel<false>, "attn_core_bwd")) return e;
-    if (int e = attn_lds(&attn_bwd_kernel<true>, "attn_core_bwd")) return e;
-    configured = true;
-  }
+  static unsigned long long reserved[2] = {0, 0};      // per kernel instantiation: bit per device
+  if (int e = attn_lds(&attn_bwd_kernel<false>, "attn_core_bwd", &reserved[0])) return e;
+  if (int e = attn_lds(&attn_bwd_kernel<true>, "attn_core_bwd", &reserved[1])) return e;
   const size_t bytes = AT_LDS_FLOATS * sizeof(float);
   if (compute_bf16()) hipLaunchKernelGGL(attn_bwd_kernel<true>, dim3(B * H * 8), dim3(256), bytes, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(attn_bwd_kernel<false>, dim3(B * H * 8), dim3(256), bytes, (hipStream_t)stream, a);

@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/demf_hip.h"
+#include "switches.h"   // sw(): the A/B switches, read from the environment once
 
 namespace demf {
 

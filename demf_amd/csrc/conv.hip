@@ -21,7 +21,6 @@
 // Also here: the 3x3 stride-2 max-pool, NCHW -> NHWC4 of the input image, and GroupNorm over NHWC rows written
 // straight into the encoder's token buffer (B, S, 256) - the channels-last hand-over needs no transposition.
 #include "common.h"
-#include <stdlib.h>
 
 namespace demf {
 
@@ -611,17 +610,15 @@ extern "C" int demf_conv_nhwc_f32(int B, int H, int W, int Cin, int Cout, int KH
   a.ksteps = cdiv(a.K / 32, ksplit);
   DEMF_REQUIRE((long long)B * H * W * Cin < (1ll << 31) && H < 16384 && W < 16384, "conv_nhwc: input too large for 32-bit offsets");
   hipStream_t s = (hipStream_t)stream;
-  static const int stream64 = getenv("DEMF_CONV_STREAM64") ? atoi(getenv("DEMF_CONV_STREAM64")) : 1;   // A/B switch
-  if (stream64 && Cin == 64 && KH == 1 && KW == 1 && stride == 1 && pad == 0 && ksplit == 1 && (Cout == 256 || Cout == 64) &&
+  if (sw().conv_stream64 && Cin == 64 && KH == 1 && KW == 1 && stride == 1 && pad == 0 && ksplit == 1 && (Cout == 256 || Cout == 64) &&
       (long long)B * H * W >= 16384) {
     // (-1000: this device does not grant the kernel's LDS - the tile kernel below serves the layer)
     const int rc = Cout == 256 ? (planes == 3 ? conv1x1_c64_launch<3, 8>(a, s) : conv1x1_c64_launch<1, 8>(a, s))
                                : (planes == 3 ? conv1x1_c64_launch<3, 2>(a, s) : conv1x1_c64_launch<1, 2>(a, s));
     if (rc != -1000) return rc;
   }
-  static const int streamk = getenv("DEMF_CONV_STREAMK") ? atoi(getenv("DEMF_CONV_STREAMK")) : 3;   // A/B switch (bits: 1 K = 128, 2 K = 256)
-  static const int stream_min = getenv("DEMF_CONV_STREAM_MIN") ? atoi(getenv("DEMF_CONV_STREAM_MIN")) : 16384;   // rows
-  if (streamk && KH == 1 && KW == 1 && stride == 1 && pad == 0 && ksplit == 1 && (long long)B * H * W >= stream_min) {
+  const int streamk = sw().conv_streamk;   // A/B switch (bits: 1 K = 128, 2 K = 256)
+  if (streamk && KH == 1 && KW == 1 && stride == 1 && pad == 0 && ksplit == 1 && (long long)B * H * W >= sw().conv_stream_min) {
     int rc = -1000;
     if ((streamk & 1) && Cin == 128 && Cout % 128 == 0)
       rc = planes == 3 ? conv1x1_stream_launch<3, 4, 2>(a, s) : conv1x1_stream_launch<1, 4, 2>(a, s);
@@ -629,9 +626,8 @@ extern "C" int demf_conv_nhwc_f32(int B, int H, int W, int Cin, int Cout, int KH
       rc = planes == 3 ? conv1x1_stream_launch<3, 2, 4>(a, s) : conv1x1_stream_launch<1, 2, 4>(a, s);
     if (rc != -1000) return rc;
   }
-  static const int wg3 = getenv("DEMF_CONV_WG3") ? atoi(getenv("DEMF_CONV_WG3")) : 0;       // A/B switch
   if (Cout % 128 == 0) {
-    if (planes == 3) return wg3 ? conv_launch<3, 128, false, true>(a, s) : conv_launch<3, 128, false>(a, s);
+    if (planes == 3) return sw().conv_wg3 ? conv_launch<3, 128, false, true>(a, s) : conv_launch<3, 128, false>(a, s);
     return conv_launch<1, 128, false>(a, s);
   }
   return planes == 3 ? conv_launch<3, 64, false>(a, s) : conv_launch<1, 64, false>(a, s);

@@ -16,7 +16,6 @@
 // tiles, 4 waves x one 32x32 MFMA accumulator, K staged in steps of 32 through LDS (fragment trick
 // of mlp.hip: a lane feeds component m of its float4 along K to MFMA m).
 #include "common.h"
-#include <stdlib.h>
 #include <type_traits>
 #include "rng.h"
 
@@ -703,11 +702,6 @@ __global__ __launch_bounds__(256, 3) void gemm_tn_group_kernel(GemmGroup g) {
 // staging mode of an operand with rows R, reduction K, strides (sr, sk).  Global dwordx4 loads only
 // need 4-byte alignment on gfx9 (parameters live at arbitrary float offsets of the flat optimizer
 // buffer), so contiguity and a length that is a multiple of 4 are the only requirements.
-static int env_tiles() {
-  static const int v = getenv("DEMF_GEMM_SMALL_TILES") ? atoi(getenv("DEMF_GEMM_SMALL_TILES")) : 1024;
-  return v;
-}
-
 static int stage_mode(long long sr, long long sk, int R, int K) {
   if (sk == 1 && K % 4 == 0) return 1;
   if (sr == 1 && R % 4 == 0) return 2;
@@ -1125,7 +1119,7 @@ static int gemm_validate(const GemmArgs& p) {
 
 static bool gemm_is_small(const GemmArgs& p) {
   const long long tiles = (long long)cdiv(p.N, G_BN) * cdiv(p.M, G_BM) * p.batch * p.splitk;
-  return tiles <= env_tiles() || p.N <= 32;
+  return tiles <= sw().gemm_small_tiles || p.N <= 32;
 }
 
 extern "C" int demf_gemm_f32(const demf_gemm_desc* d, demf_stream_t stream) {
@@ -1212,9 +1206,7 @@ extern "C" int demf_gemm_group_f32(const demf_gemm_desc* descs, int n, demf_stre
   const bool bf = compute_bf16();
   // modes 1 / 2: the 64 x 64-tile kernel on the bf16 matrix cores (one / three terms per operand); mode 0
   // (native fp32 MFMA) keeps the 32 x 32-tile kernel
-  static const bool tn_off = getenv("DEMF_GEMM_TN3") && atoi(getenv("DEMF_GEMM_TN3")) == 0;   // A/B switch
-  const bool tn3 = compute_mode() != 0 && !tn_off;
-  static const int tn_split = getenv("DEMF_GEMM_TN_SPLIT") ? atoi(getenv("DEMF_GEMM_TN_SPLIT")) : 0;   // A/B: forced K split
+  const bool tn3 = compute_mode() != 0 && sw().gemm_tn3 != 0;   // A/B switch
   int i0 = 0;
   while (i0 < n) {
     // longest run of consecutive problems that can share one launch: small-tile path, both operands
@@ -1246,7 +1238,7 @@ extern "C" int demf_gemm_group_f32(const demf_gemm_desc* descs, int n, demf_stre
       // gradients of a decoder layer, 252 tiles: 8 slices 60 us, 3 slices 51 us, 2 slices 56 us)
       int base = 0;
       for (int i = 0; i < cnt; ++i) base += cdiv(g.p[i].N, 64) * cdiv(g.p[i].M, 64) * g.p[i].batch;
-      const int want = tn_split > 0 ? tn_split : (768 + base / 2) / base;
+      const int want = sw().gemm_tn_split > 0 ? sw().gemm_tn_split : (768 + base / 2) / base;
       tiles = 0;
       for (int i = 0; i < cnt; ++i) {
         GemmArgs& q = g.p[i];
@@ -1257,8 +1249,7 @@ extern "C" int demf_gemm_group_f32(const demf_gemm_desc* descs, int n, demf_stre
     }
     g.start[cnt] = tiles;
     g.n = cnt;
-    static const int tn_dbg = getenv("DEMF_TN_DBG") ? atoi(getenv("DEMF_TN_DBG")) : 0;   // phase-skip timing experiments
-    g.dbg = tn_dbg;
+    g.dbg = sw().tn_dbg;   // phase-skip timing experiments
     if (tn3) {
       if (bf) hipLaunchKernelGGL((gemm_tn_group_kernel<1>), dim3(tiles), dim3(256), 0, (hipStream_t)stream, g);
       else hipLaunchKernelGGL((gemm_tn_group_kernel<3>), dim3(tiles), dim3(256), 0, (hipStream_t)stream, g);
@@ -1321,7 +1312,7 @@ extern "C" int demf_add_dropout_ln_bwd(int R, int C, const float* dy, const floa
   DEMF_REQUIRE(p == 0.f || rng, "add_dropout_ln_bwd: dropout needs the rng state");
   // ~256 blocks (one per CU): each wave walks rows_per_wave rows one after the other (two wave
   // reductions per row, ~2 us each), so a column sees <= 256 atomics
-  static const int ln_blocks = getenv("DEMF_LN_BWD_BLOCKS") ? max(1, atoi(getenv("DEMF_LN_BWD_BLOCKS"))) : 256;
+  const int ln_blocks = max(1, sw().ln_bwd_blocks);
   const int rpw = max(1, cdiv(R, ln_blocks * 4));
   const int blocks = cdiv(R, 4 * rpw);
 #define CALL(V) hipLaunchKernelGGL(add_dropout_ln_bwd_k<V>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,  \

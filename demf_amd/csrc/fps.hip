@@ -1051,8 +1051,7 @@ static int fps_impl(int B, int N, int M, const float* xyz, float* temp, long lon
   // first (needs B ints of scratch in `temp`); scenes it verifies are skipped by the main kernel
   const int* skip = nullptr;
   if (temp != nullptr && M >= 2 && M <= FPS_PREFIX_MAX && N <= 4 * M && bs >= 64 && ppt <= 24) {
-    static const int split = [] { const char* v = getenv("DEMF_FPS_CHECK_SPLIT"); return v ? atoi(v) : 1; }();   // A/B
-    if (split && temp_floats >= (long long)B * (M + 2) && cdiv(N, 32) < 0x8000) {
+    if (sw().fps_check_split && temp_floats >= (long long)B * (M + 2) && cdiv(N, 32) < 0x8000) {
       int* flag = (int*)temp;
       int* ticket = flag + B;
       float* E = temp + 2 * (size_t)B;
@@ -1064,21 +1063,18 @@ static int fps_impl(int B, int N, int M, const float* xyz, float* temp, long lon
     skip = (const int*)temp;
   }
   // large clouds with the (B, N) scratch at hand: Hilbert-cell order + the exact box-pruned kernel
-  static const int prune_on = [] { const char* v = getenv("DEMF_FPS_PRUNE"); return v ? atoi(v) : 1; }();
-  if (prune_on && skip == nullptr && temp != nullptr && bs == 1024 && N >= 4096 && N <= 20 * 1024 && M >= 64 &&
+  if (sw().fps_prune && skip == nullptr && temp != nullptr && bs == 1024 && N >= 4096 && N <= 20 * 1024 && M >= 64 &&
       M <= N) {
     int* perm = (int*)temp;
     hipLaunchKernelGGL(fps_sort_k, dim3(B), dim3(1024), 0, s, N, xyz, perm);
     // per-pair cached maxima instead of the 20-slot re-search (round 6).  Measured on MI355X (tools/fps_micro.py):
     // 20 000 -> 2 048: 2 364 vs 2 420 cycles per round; 16 384 -> 2 048: 2 234 vs 2 184 (fewer slots: the search it
     // replaces is shorter) - so the default takes it above 16 slots per lane only.  DEMF_FPS_PAIR = 0 / 1 forces.
-    static const int pair_env = [] { const char* v = getenv("DEMF_FPS_PAIR"); return v ? atoi(v) : -1; }();
-    const bool pair_on = pair_env < 0 ? ppt > 16 : pair_env != 0;
+    const bool pair_on = sw().fps_pair < 0 ? ppt > 16 : sw().fps_pair != 0;
     if (pair_on) {
 #define PAIR(P) hipLaunchKernelGGL((fps_pair_kernel<P>), dim3(B), dim3(1024), 0, s, N, M, xyz, perm, idx)
 #define PAIR8(P) hipLaunchKernelGGL((fps_pair_kernel<P, 8>), dim3(B), dim3(512), 0, s, N, M, xyz, perm, idx)
-      static const int pwaves = [] { const char* v = getenv("DEMF_FPS_PAIR_WAVES"); return v ? atoi(v) : 16; }();   // A/B
-      if (pwaves == 8 && ppt > 8) {
+      if (sw().fps_pair_waves == 8 && ppt > 8) {   // A/B
         if (ppt <= 12) PAIR8(24); else if (ppt <= 16) PAIR8(32); else PAIR8(40);
       } else if (ppt <= 4) PAIR(4); else if (ppt <= 8) PAIR(8); else if (ppt <= 12) PAIR(12);
       else if (ppt <= 16) PAIR(16); else PAIR(20);
@@ -1090,8 +1086,7 @@ static int fps_impl(int B, int N, int M, const float* xyz, float* temp, long lon
 #define PRUNE8(P) hipLaunchKernelGGL((fps_prune_kernel<P, 8>), dim3(B), dim3(512), 0, s, N, M, xyz, perm, idx)
     // A/B switch, default 16: 8 waves x 40 slots is bit-identical but SLOWER (20 000 -> 2 048: 2 643 vs 2 058 us) -
     // the round's critical path is the wave that has to update and search again, and that wave's work doubles
-    static const int waves = [] { const char* v = getenv("DEMF_FPS_WAVES"); return v ? atoi(v) : 16; }();
-    if (waves == 8 && ppt > 8) {                            // 8 waves x up to 40 slots per lane
+    if (sw().fps_waves == 8 && ppt > 8) {                            // 8 waves x up to 40 slots per lane
       if (ppt <= 12) PRUNE8(24); else if (ppt <= 16) PRUNE8(32); else PRUNE8(40);
     } else if (ppt <= 4) PRUNE(4); else if (ppt <= 8) PRUNE(8); else if (ppt <= 12) PRUNE(12);
     else if (ppt <= 16) PRUNE(16); else PRUNE(20);          // 24 slots + their keys spill

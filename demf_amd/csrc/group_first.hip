@@ -327,8 +327,7 @@ extern "C" int demf_group_first_fwd(int B, int N, int M, int ns, int C1, float r
   long long blocks = (chunks + gpb - 1) / gpb;
   // (one fp64 add per column per block; with the statistics in replicated accumulators the tail no longer argues for
   //  few blocks - resident step 256 / 512 / 1024 blocks: 4.44 / 4.42 / 4.39 ms)
-  static const int fcap = getenv("DEMF_GF_FWD_BLOCKS") ? atoi(getenv("DEMF_GF_FWD_BLOCKS")) : 1024;
-  if (blocks > fcap) blocks = fcap;
+  if (blocks > sw().gf_fwd_blocks) blocks = sw().gf_fwd_blocks;
   const dim3 grid((unsigned)blocks);
   // train-mode BatchNorm bookkeeping (demf_bn_finalize's arguments): by the launch's last workgroup when a counter set
   // and an accumulator block are to be had, as a launch behind this one otherwise
@@ -337,8 +336,7 @@ extern "C" int demf_group_first_fwd(int B, int N, int M, int ns, int C1, float r
   if (want_fin) {
     DEMF_REQUIRE(stats && gamma && beta && mean_invstd, "group_first_fwd: the BatchNorm bookkeeping needs stats, gamma, "
                  "beta, scale_shift and mean_invstd");
-    static const bool fin_off = getenv("DEMF_GF_FIN") && atoi(getenv("DEMF_GF_FIN")) == 0;   // A/B switch
-    int* ticket = fin_off ? nullptr : sched_slot();
+    int* ticket = sw().gf_fin == 0 ? nullptr : sched_slot();   // A/B switch
     double* racc = ticket ? accum_slot() : nullptr;
     if (ticket != nullptr && racc != nullptr)
       fin = BnFin{(double)rows, gamma, beta, conv_bias, eps, momentum, running_mean, running_var, num_batches_tracked,
@@ -370,8 +368,7 @@ extern "C" int demf_group_first_bwd(int B, int N, int M, int ns, int C1, float r
   DEMF_REQUIRE(xyz && center && G && (Y || U) && vec6 && inv_off && inv_rows && dU && dWx,
                "group_first_bwd: null pointer");
   DEMF_REQUIRE(U == nullptr || Wx != nullptr, "group_first_bwd: forming y again from U needs the layer's weight");
-  static const bool rc_off = getenv("DEMF_GF_RECOMPUTE") && atoi(getenv("DEMF_GF_RECOMPUTE")) == 0;   // A/B switch
-  const bool rc = U != nullptr && !(rc_off && Y != nullptr);
+  const bool rc = U != nullptr && !(sw().gf_recompute == 0 && Y != nullptr);   // A/B switch
   const float div = normalize_xyz ? radius : 1.0f;
   const long long points = (long long)B * N;
   const float inv_div = normalize_xyz ? 1.0f / radius : 1.0f;
@@ -380,13 +377,11 @@ extern "C" int demf_group_first_bwd(int B, int N, int M, int ns, int C1, float r
   hipStream_t s = (hipStream_t)stream;
   const int lpr = C1 / 4, gpb = 256 / lpr;
   long long blocks = (points + gpb - 1) / gpb;
-  static const bool wacc_off = getenv("DEMF_GF_WACC") && atoi(getenv("DEMF_GF_WACC")) == 0;   // A/B switch
-  int* ticket = wacc && !wacc_off ? sched_slot() : nullptr;
+  int* ticket = wacc && sw().gf_wacc != 0 ? sched_slot() : nullptr;   // A/B switch
   if (ticket == nullptr) wacc = nullptr;          // (no counter set: every workgroup adds to dWx itself)
   // (one group per source point and pass: more workgroups = more independent load chains in flight; the partial dWx of
   //  a workgroup go to one of GF_REPL copies of the accumulator, so the cap no longer trades against the atomic tail)
-  static const int bcap = getenv("DEMF_GF_BWD_BLOCKS") ? atoi(getenv("DEMF_GF_BWD_BLOCKS")) : 0;
-  const int cap = bcap > 0 ? bcap : (dxyz == nullptr && wacc != nullptr ? 2048 : 1024);
+  const int cap = sw().gf_bwd_blocks > 0 ? sw().gf_bwd_blocks : (dxyz == nullptr && wacc != nullptr ? 2048 : 1024);
   if (blocks > cap) blocks = cap;
   const dim3 grid((unsigned)blocks);
   DEMF_REQUIRE((dxyz == nullptr) == (dcenter == nullptr) && (dxyz == nullptr || Wx != nullptr),

@@ -10,7 +10,6 @@
 // All of these are pure HBM/L2 byte movers: the roofline is bytes written + bytes
 // gathered over 8 TB/s.
 #include "common.h"
-#include <stdlib.h>
 
 namespace demf {
 
@@ -799,8 +798,7 @@ extern "C" int demf_colsum_f32(int R, int N, int ld, const float* x, float* out,
   // at most ~256 blocks: each ends in N same-address atomics, which serialise in L2
   // and at least DEMF_COLSUM_ROWS rows per block (2 k-row layers: 32 blocks, atomic depth 32)
   int rpb = (R + 255) / 256;
-  static const int min_rows = [] { const char* v = getenv("DEMF_COLSUM_ROWS"); return v ? atoi(v) : 64; }();
-  rpb = rpb < min_rows ? min_rows : rpb;
+  rpb = rpb < sw().colsum_rows ? sw().colsum_rows : rpb;
   const dim3 grid((R + rpb - 1) / rpb);
   if (N % 4 == 0 && ld % 4 == 0 && ((size_t)x & 15) == 0)
     hipLaunchKernelGGL(colsum_k<4>, grid, dim3(256), 0, (hipStream_t)stream, R, N, ld, rpb, x, out);
@@ -824,16 +822,10 @@ extern "C" int demf_invert_index(int B, int N, int E, const int* idx, int* off, 
   if (lds + sizeof(int) * (size_t)E <= 150 * 1024) {
     lds += sizeof(int) * (size_t)E;
     lds_rows = 1;
-    static bool attr_set = false;
-    if (!attr_set) {
-      if (hipFuncSetAttribute((const void*)invert_index_k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              150 * 1024) != hipSuccess) {
-        (void)hipGetLastError();
-        lds -= sizeof(int) * (size_t)E;
-        lds_rows = 0;
-      } else {
-        attr_set = true;
-      }
+    static unsigned long long reserved = 0;      // bit per device
+    if (!reserve_lds((const void*)invert_index_k, 150 * 1024, &reserved)) {
+      lds -= sizeof(int) * (size_t)E;
+      lds_rows = 0;
     }
   }
   hipLaunchKernelGGL(invert_index_k, dim3(B), dim3(1024), lds, (hipStream_t)stream, N, E, idx, off,
@@ -846,7 +838,7 @@ extern "C" int demf_invert_index_ws(int B, int N, int E, const int* idx, int* of
   DEMF_REQUIRE(B >= 0 && N >= 1 && E >= 0, "invert_index_ws: bad sizes");
   if (B == 0) return DEMF_OK;
   DEMF_REQUIRE(idx && off && rows, "invert_index_ws: null pointer");
-  static const int split = [] { const char* v = getenv("DEMF_INVERT_SPLIT"); return v ? atoi(v) : 1; }();   // A/B switch
+  const int split = sw().invert_split;   // A/B switch
   // The one-workgroup-per-scene form keeps its lists in LDS while they fit (150 KB: SA2's 32 768 entries over 2 048
   // points just do).  Alone on the GPU the five-launch split form is the faster one from ~28 k entries on, but the
   // inversion belongs to the coordinate pre-pass, which the training loop runs on a side stream UNDER the previous

@@ -44,11 +44,6 @@ using bf16x4 = __bf16 __attribute__((ext_vector_type(4)));
 //       (the dropped m.l, l.m, l.l terms are <= 2^-23 relative - the rounding of one fp32 FMA).
 //       On gfx950 the bf16 MFMA runs 16x the fp32 one, so six of them cost 3/8 of the native fp32
 //       issue time at fp32-grade results (tests/test_gpu_split.py measures both against fp64).
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
 // Until demf_set_compute_dtype is called the mode is 2, or 0 with DEMF_F32_NATIVE=1 in the environment.
 static std::atomic<int> g_compute_mode{-1};
 // demf_ctx_push / demf_ctx_pop: the calling THREAD's mode for the calls in between (a stack, so library code
@@ -61,8 +56,7 @@ int compute_mode() {
   if (tl_mode_top > 0 && tl_mode_stack[tl_mode_top - 1] >= 0) return tl_mode_stack[tl_mode_top - 1];
   int m = g_compute_mode.load(std::memory_order_relaxed);
   if (m < 0) {
-    const char* v = getenv("DEMF_F32_NATIVE");
-    m = (v && atoi(v)) ? 0 : 2;
+    m = sw().f32_native ? 0 : 2;
     g_compute_mode.store(m);
   }
   return m;
@@ -73,8 +67,7 @@ static std::atomic<int> g_f16_terms{-1};
 bool f16_terms() {
   int on = g_f16_terms.load(std::memory_order_relaxed);
   if (on < 0) {
-    const char* v = getenv("DEMF_F16_TERMS");
-    on = v ? (atoi(v) != 0) : 1;
+    on = sw().f16_terms != 0;
     g_f16_terms.store(on);
   }
   return on && compute_mode() == 2;
@@ -2161,7 +2154,7 @@ int* sched_slot() {
     if (hipGetSymbolAddress(&ptr, HIP_SYMBOL(g_tile_sched)) != hipSuccess) return nullptr;
     base = (int*)ptr;
   }
-  if (env_int("DEMF_STATIC_TILES", 0)) return nullptr;     // A/B switch
+  if (sw().static_tiles) return nullptr;     // A/B switch
   return base + SCHED_INTS * (next.fetch_add(1) % SCHED_SLOTS);
 }
 
@@ -2177,13 +2170,13 @@ double* accum_slot() {
     if (hipGetSymbolAddress(&ptr, HIP_SYMBOL(g_accum_ring)) != hipSuccess) return nullptr;
     base = (double*)ptr;
   }
-  if (!env_int("DEMF_ACC_REPL", 1)) return nullptr;     // A/B switch
+  if (!sw().acc_repl) return nullptr;     // A/B switch
   return base + (size_t)ACC_SLOT_DOUBLES * (next.fetch_add(1) % ACC_SLOTS);
 }
 
 static int mlp_grid(int R, int brows) {
   const int tiles = (R + brows - 1) / brows;
-  const int cap = env_int("DEMF_GEMM_GRID", 256 * 2);   // persistent: two 256-thread blocks per CU
+  const int cap = sw().gemm_grid;   // persistent: two 256-thread blocks per CU (256 * 2)
   return tiles < cap ? (tiles > 0 ? tiles : 1) : cap;
 }
 
@@ -2645,8 +2638,7 @@ static int launch_gemm(const MlpArgs& a, hipStream_t s) {
     case 1: return launch_gemm_t<PRO, STATS, POOL, RED, 1>(a, s);
     case 2: {
       // A/B switch: DEMF_X3_MASK bit 0 = forward launches, bit 1 = input-gradient, bit 2 = weight-gradient
-      static const int mask = env_int("DEMF_X3_MASK", 7);
-      if (mask & (PRO >= PRO_DY_DENSE ? 2 : 1)) return launch_gemm_t<PRO, STATS, POOL, RED, 2>(a, s);
+      if (sw().x3_mask & (PRO >= PRO_DY_DENSE ? 2 : 1)) return launch_gemm_t<PRO, STATS, POOL, RED, 2>(a, s);
       return launch_gemm_t<PRO, STATS, POOL, RED, 0>(a, s);
     }
     default: return launch_gemm_t<PRO, STATS, POOL, RED, 0>(a, s);
@@ -2657,29 +2649,22 @@ template <int PRO, bool STATS, bool POOL, bool RED, int BF16>
 static int launch_gemm_t(const MlpArgs& a, hipStream_t s) {
   if constexpr ((BF16 == 1 || BF16 == 2) && !RED && STATS && PRO == PRO_BNRELU) {
     // producer / consumer forward for 128-channel inputs (mlp_fwd_pc_kernel): SA2-4 and the vote aggregation
-    static const int pc_on = env_int("DEMF_FWD_PC", 1);
-    static const int pc_min_r = env_int("DEMF_FWD_PC_MIN_R", 16384);
     const bool pc_sel = !POOL || (a.pmin == nullptr && a.fin.gamma != nullptr && a.pmax && a.amax);
-    if (pc_on && a.st == 0 && a.K == PC_K && (a.N == 128 || a.N == 256) && a.ldx == PC_K && a.ldy == a.N &&
-        a.ldb == 0 && pc_sel && a.R >= pc_min_r && a.R % PC_ROWS == 0 && a.vec != nullptr && a.stats != nullptr &&
+    if (sw().fwd_pc && a.st == 0 && a.K == PC_K && (a.N == 128 || a.N == 256) && a.ldx == PC_K && a.ldy == a.N &&
+        a.ldb == 0 && pc_sel && a.R >= sw().fwd_pc_min_r && a.R % PC_ROWS == 0 && a.vec != nullptr && a.stats != nullptr &&
         (!POOL || a.ns == 16 || a.ns == 32) && (a.fin.ss == nullptr || a.fin.ticket != nullptr)) {
-      static const int cus = [] { const char* v = getenv("DEMF_PERSIST_CUS"); return v ? atoi(v) : 240; }();
       const int nslab = a.R / PC_ROWS, halves = a.N / 128;
-      int gh = cus / halves;                       // workgroups per column half
+      int gh = sw().persist_cus / halves;                       // workgroups per column half
       if (gh > nslab) gh = nslab;
       if (halves == 2) gh = gh / 8 * 8 > 0 ? gh / 8 * 8 : 8;   // interleaved halves: runs of 8 blocks
 #define PCGO(CMv)                                                                                              \
       do {                                                                                                     \
         constexpr int P = CMv == 2 ? 3 : (CMv == 3 ? 2 : 1);                                                   \
         const size_t bytes = (size_t)2 * P * PC_ROWS * PC_KB;                                                  \
-        static bool configured = false;                                                                        \
-        if (!configured) {                                                                                     \
-          if (hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fwd_pc_kernel<CMv, POOL>),                \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {     \
-            set_error("mlp_fwd_pc: cannot reserve %zu bytes of LDS", bytes);                                   \
-            return DEMF_ELAUNCH;                                                                               \
-          }                                                                                                    \
-          configured = true;                                                                                   \
+        static unsigned long long reserved = 0;      /* bit per device */                                     \
+        if (!reserve_lds(reinterpret_cast<const void*>(&mlp_fwd_pc_kernel<CMv, POOL>), (int)bytes, &reserved)) { \
+          set_error("mlp_fwd_pc: cannot reserve %zu bytes of LDS", bytes);                                     \
+          return DEMF_ELAUNCH;                                                                                 \
         }                                                                                                      \
         hipLaunchKernelGGL((mlp_fwd_pc_kernel<CMv, POOL>), dim3(gh * halves), dim3(512), bytes, s, a);         \
       } while (0)
@@ -2691,9 +2676,8 @@ static int launch_gemm_t(const MlpArgs& a, hipStream_t s) {
       return check_launch("mlp_fwd_pc");
     }
     // weight-resident, barrier-free forward (mlp_fwd_res_kernel): 64-channel inputs, N = 64 / 128
-    static const int fr_on = env_int("DEMF_FWD_RES", 1);
     const bool sel = !POOL || (a.pmin == nullptr && a.fin.gamma != nullptr);
-    if ((fr_on || a.st) && a.K == 64 && (a.N == 64 || a.N == 128) && (a.ldx == 64 || (a.st == 8 && a.ldx == 4)) &&
+    if ((sw().fwd_res || a.st) && a.K == 64 && (a.N == 64 || a.N == 128) && (a.ldx == 64 || (a.st == 8 && a.ldx == 4)) &&
         a.ldy == a.N && a.ldb == 0 && sel &&
         a.R >= 64 * 256 && (!POOL || ((a.ns == 16 || a.ns == 32 || a.ns == 64) && a.R % 64 == 0)) &&
         (a.fin.ss == nullptr || a.fin.ticket != nullptr)) {
@@ -2705,18 +2689,14 @@ static int launch_gemm_t(const MlpArgs& a, hipStream_t s) {
       int gx = (nunit + FR_NW - 1) / FR_NW;
       // one 8-wave workgroup per CU, on 240 of the 256: the rest is left to the resident FPS chain of
       // the next batch (csrc/mlp_bwd.hip launch_fused has the measurements)
-      static const int cus = env_int("DEMF_PERSIST_CUS", 240);
-      if (gx > cus) gx = cus;
+      if (gx > sw().persist_cus) gx = sw().persist_cus;
 #define FRGO_(NTNv, STv, CMv)                                                                               \
       do {                                                                                                  \
-        static bool configured = false;                                                                     \
-        if (!configured) {                                                                                  \
-          if (hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fwd_res_kernel<NTNv, 2, POOL, CMv, STv>),   \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {   \
-            set_error("mlp_fwd_res: cannot reserve %zu bytes of LDS", bytes);                                \
-            return DEMF_ELAUNCH;                                                                             \
-          }                                                                                                 \
-          configured = true;                                                                                \
+        static unsigned long long reserved = 0;      /* bit per device */                                  \
+        if (!reserve_lds(reinterpret_cast<const void*>(&mlp_fwd_res_kernel<NTNv, 2, POOL, CMv, STv>), (int)bytes,  \
+                         &reserved)) {                                                                      \
+          set_error("mlp_fwd_res: cannot reserve %zu bytes of LDS", bytes);                                 \
+          return DEMF_ELAUNCH;                                                                              \
         }                                                                                                   \
         hipLaunchKernelGGL((mlp_fwd_res_kernel<NTNv, 2, POOL, CMv, STv>), dim3(gx), dim3(64 * FR_NW), bytes, s, a); \
       } while (0)
@@ -2762,10 +2742,8 @@ static int launch_gemm_t(const MlpArgs& a, hipStream_t s) {
   }
   if constexpr ((BF16 == 1 || BF16 == 2) && !POOL && !STATS && (PRO == PRO_DY_DENSE || PRO == PRO_DY_SPARSE)) {
     // few-row input-gradient launches on the tile kernel (mlp_dx_tile_kernel); A/B switch DEMF_DX_TILE
-    static const int dxt_on = env_int("DEMF_DX_TILE", 1);
-    static const int dxt_max_r = env_int("DEMF_DX_TILE_MAX_R", 16384);
     constexpr bool SP = PRO == PRO_DY_SPARSE;
-    if (dxt_on && a.R <= dxt_max_r && a.K % 32 == 0 && a.K >= 64 && a.K <= 1024 && a.N % 64 == 0 && a.ldx % 4 == 0 &&
+    if (sw().dx_tile && a.R <= sw().dx_tile_max_r && a.K % 32 == 0 && a.K >= 64 && a.K <= 1024 && a.N % 64 == 0 && a.ldx % 4 == 0 &&
         a.ldb > 0 && a.vec != nullptr && ((uintptr_t)a.X % 16 == 0) && (SP ? (a.dP && a.arg && a.ns >= 1) : (a.G != nullptr)) &&
         (SP ? ((uintptr_t)a.dP % 16 == 0 && (uintptr_t)a.arg % 16 == 0) : ((uintptr_t)a.G % 16 == 0)) &&
         (!RED || (a.fY && a.fss && a.fmi && a.stats))) {
@@ -2776,11 +2754,9 @@ static int launch_gemm_t(const MlpArgs& a, hipStream_t s) {
   }
   if constexpr ((BF16 == 1 || BF16 == 2) && !RED && !POOL && STATS && (PRO == PRO_BNRELU || PRO == PRO_NONE)) {
     // few-row forward layers on the 64 x 64 tile kernel (mlp_fwd_tile_kernel); A/B switch DEMF_FWD_TILE
-    static const int tile_on = env_int("DEMF_FWD_TILE", 1);
     // (measured, tools/fewrow_fwd_micro.py: 4 096 x 512 -> 256 26.3 -> 17.3 us, 8 192 x 512 -> 256 33.3 -> 23.7,
     // 2 048 x 256 -> 128 14.3 -> 10.2; at 32 768 rows mlp_gemm_kernel's 128-row tiles are level again: 43.6 vs 45.6)
-    static const int tile_max_r = env_int("DEMF_FWD_TILE_MAX_R", 16384);
-    if (tile_on && a.R <= tile_max_r && a.K % 32 == 0 && a.K >= 64 && a.K <= 1024 && a.N % 64 == 0 && a.ldx % 4 == 0 &&
+    if (sw().fwd_tile && a.R <= sw().fwd_tile_max_r && a.K % 32 == 0 && a.K >= 64 && a.K <= 1024 && a.N % 64 == 0 && a.ldx % 4 == 0 &&
         a.ldb == 0 && a.ldy % 1 == 0 && a.stats != nullptr && a.fin.ss != nullptr && a.fin.ticket != nullptr &&
         ((uintptr_t)a.X % 16 == 0) && ((uintptr_t)a.Bt % 16 == 0) && (PRO == PRO_NONE || a.vec != nullptr)) {
       constexpr int P = BF16 == 2 ? 3 : 1;
@@ -2810,7 +2786,7 @@ static int launch_gemm_t(const MlpArgs& a, hipStream_t s) {
     // prefetch and the epilogue's temporaries fit in 256 VGPRs - wider outputs go to blockIdx.y
     // ns = 64: 64-row wave tiles x <= 2 column tiles (column halves co-scheduled), or - when all the
     // columns fit 4 tiles - 32-row wave tiles x 4 column tiles with the group merged across a wave pair
-    const bool half64 = a.ns == 64 && nt <= 4 && !env_int("DEMF_POOL_HALVES", 0);
+    const bool half64 = a.ns == 64 && nt <= 4 && !sw().pool_halves;
     const bool rt2 = a.ns == 64 && !half64;
     const int ntl = rt2 ? (nt < 2 ? nt : 2) : (nt < 4 ? nt : 4);
     const int ys = (nt + ntl - 1) / ntl;
@@ -2827,8 +2803,7 @@ static int launch_gemm_t(const MlpArgs& a, hipStream_t s) {
     {
       const int brows = rt2 ? 256 : 128;
       const int tiles = (a.R + brows - 1) / brows;
-      static const int pool_dyn = env_int("DEMF_POOL_DYN", 1);
-      if (pool_dyn && ys == 1 && tiles > gx && a.K > MLP_BK && gx % (8 * SCHED_GROUPS) == 0)
+      if (sw().pool_dyn && ys == 1 && tiles > gx && a.K > MLP_BK && gx % (8 * SCHED_GROUPS) == 0)
         a2.sched = sched_slot();
     }
     // SEL: only the extremum the sign of gamma selects (pmin / amin not given, gamma known)
@@ -2849,10 +2824,8 @@ static int launch_gemm_t(const MlpArgs& a, hipStream_t s) {
   const int tiles1 = (a.R + 127) / 128;
   // (three-term mode: more than 4 column tiles per block would not leave LDS for two blocks per CU -
   // the columns go to blockIdx.y instead of the launch falling back to the fp32 MFMA)
-  static const int wide_split = env_int("DEMF_X3_WIDE_SPLIT", 1);
-  if ((tiles1 < 192 && nt > 1) || nt > NT_MAX || (BF16 == 2 && nt > 4 && wide_split)) {
-    static const int split_target = env_int("DEMF_SPLIT_TARGET", 256);   // blocks the column split aims at
-    int ysplit = (split_target + tiles1 - 1) / tiles1;
+  if ((tiles1 < 192 && nt > 1) || nt > NT_MAX || (BF16 == 2 && nt > 4 && sw().x3_wide_split)) {
+    int ysplit = (sw().split_target + tiles1 - 1) / tiles1;   // (the blocks the column split aims at)
     if (ysplit < (nt + 3) / 4) ysplit = (nt + 3) / 4;     // at most 4 column tiles per block
     if (ysplit > nt) ysplit = nt;
     const int ntl = (nt + ysplit - 1) / ysplit;          // column tiles per block
@@ -3010,12 +2983,11 @@ extern "C" int demf_mlp_gemm_fwd_pool(int R, int K, int N, int ldx, const float*
 // available, as a separate launch otherwise (DEMF_STATIC_TILES=1, DEMF_NO_FIN=1)
 template <typename Launch>
 static int launch_with_finalize(MlpArgs& a, BnFin fin, Launch launch, hipStream_t s) {
-  static const int off = env_int("DEMF_NO_FIN", 0);
-  fin.ticket = off ? nullptr : sched_slot();
+  fin.ticket = sw().no_fin ? nullptr : sched_slot();
   // (replicated accumulators: measured neutral on the forward launches - their workgroups do not end together (the
   //  persistent SA kernels) or the 8 x 2N exchanges of the finalize cost what the shorter queue saves (the 64 x 64-tile
   //  kernel) - so off unless DEMF_ACC_REPL_FWD=1; the row-reduction kernels of the BN backward gain 2-5 us each)
-  fin.racc = fin.ticket != nullptr && a.N <= ACC_MAX_N && env_int("DEMF_ACC_REPL_FWD", 0) ? accum_slot() : nullptr;
+  fin.racc = fin.ticket != nullptr && a.N <= ACC_MAX_N && sw().acc_repl_fwd ? accum_slot() : nullptr;
   a.fin = fin;
   if (fin.ticket != nullptr) return launch(a);
   a.fin.ss = nullptr;                     // (gamma stays: the pooled epilogue selects by its sign)
@@ -3323,7 +3295,7 @@ static int bn_bwd_reduce_impl(int R, int N, int ns, const float* G, const float*
                "bn_bwd_reduce: null pointer");
   // (a "pooled" layer with one sample per group - the row MLPs of the FP / vote / head modules - is the
   // dense case: dP is the upstream gradient of every row and the selected row is the row itself)
-  if (!G && ns == 1 && !y_bf16 && N % 4 == 0 && N <= 1024 && env_int("DEMF_BNRED_NS1_DENSE", 1)) G = dP;
+  if (!G && ns == 1 && !y_bf16 && N % 4 == 0 && N <= 1024 && sw().bnred_ns1_dense) G = dP;
   if (G && N % 4 == 0 && N <= 1024) {
     const int rp = 256 / (N / 4);
     // few blocks: every block ends with 2N same-address fp64 atomics, which serialise in L2
@@ -3332,22 +3304,22 @@ static int bn_bwd_reduce_impl(int R, int N, int ns, const float* G, const float*
     //  two unrolled passes of 4 row groups per workgroup, up to 1024 of them; measured on the resident step: 4 row groups
     //  4.233, 8 4.208, 16 4.208-4.218 ms; without the copies (16 per workgroup, <= 256 of them) 4.248)
     const bool repl = vf.ticket != nullptr && vf.racc != nullptr;
-    int grid = cdiv(R, rp * (repl ? env_int("DEMF_BNRED_RPB", 8) : 16));
-    const int cap = env_int("DEMF_BNRED_GRID", repl ? 1024 : 256);
+    int grid = cdiv(R, rp * (repl ? sw().bnred_rpb : 16));
+    const int cap = sw().bnred_grid >= 0 ? sw().bnred_grid : (repl ? 1024 : 256);
     if (grid > cap) grid = cap;
     hipLaunchKernelGGL(bn_bwd_reduce_dense4_k<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, R, N, G,
-                       Y, scale_shift, mean_invstd, g12, env_int("DEMF_BNRED_REV", 1), vf,
+                       Y, scale_shift, mean_invstd, g12, sw().bnred_rev, vf,
                        (const float*)nullptr, (const int*)nullptr, 1, 0);
     return check_launch("bn_bwd_reduce");
   }
   // pooled form with the selected rows' raw outputs at hand: the same float4 kernel over the R/ns pooled
   // rows (<= 256 blocks -> <= 256 same-address fp64 atomics per channel instead of 1 024: at SA1 the
   // sparse kernel's 31 us were mostly that tail)
-  if (!G && yraw && N % 4 == 0 && N <= 1024 && R % ns == 0 && env_int("DEMF_BNRED_POOLED_DENSE", 1)) {
+  if (!G && yraw && N % 4 == 0 && N <= 1024 && R % ns == 0 && sw().bnred_pooled_dense) {
     const int Rp = R / ns, rp = 256 / (N / 4);
     const bool repl = vf.ticket != nullptr && vf.racc != nullptr;
-    int grid = cdiv(Rp, rp * (repl ? env_int("DEMF_BNRED_RPB", 8) : 16));
-    const int cap = env_int("DEMF_BNRED_GRID", repl ? 1024 : 256);
+    int grid = cdiv(Rp, rp * (repl ? sw().bnred_rpb : 16));
+    const int cap = sw().bnred_grid >= 0 ? sw().bnred_grid : (repl ? 1024 : 256);
     if (grid > cap) grid = cap;
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(bn_bwd_reduce_dense4_k<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, Rp, N, dP,
@@ -3359,8 +3331,8 @@ static int bn_bwd_reduce_impl(int R, int N, int ns, const float* G, const float*
   // (measured on the training step, sparse form: caps of 256 / 128 / 64 / 32 blocks cost +0.04 / +0.21 /
   // +0.45 / +1.0 ms per step - the launch is bound by its dependent loads per block, not by the
   // 2N same-address fp64 atomics each block ends with)
-  int grid = cdiv(rows, rows_par * (G ? 8 : env_int("DEMF_BNRED_SPARSE_RPT", 8)));
-  const int scap = G ? 1024 : env_int("DEMF_BNRED_SPARSE_GRID", 1024);
+  int grid = cdiv(rows, rows_par * (G ? 8 : sw().bnred_sparse_rpt));
+  const int scap = G ? 1024 : sw().bnred_sparse_grid;
   if (grid > scap) grid = scap;
   if (grid < 1) grid = 1;
   if (G)
@@ -3431,8 +3403,7 @@ static int mlp_bwd_dx_impl(bool w_direct, int R, int N, int K, int ldo, const fl
   // Outputs wider than 128 columns: ONE launch whose column tiles are split over blockIdx.y (every
   // block rebuilds its dY row tile, as the per-chunk launches did, but the chunks now run side by side
   // instead of as 2-4 dependent launches of one block per CU each); DEMF_DX_CHUNKS=1: chunk launches.
-  static const int chunked = env_int("DEMF_DX_CHUNKS", 0);
-  const int cstep = (!chunked && K <= 512) ? K : 128;
+  const int cstep = (!sw().dx_chunks && K <= 512) ? K : 128;
   for (int c0 = 0; c0 < K; c0 += cstep) {
     // here the reduction runs over this layer's N channels and the output has K columns
     MlpArgs a{};
@@ -3447,7 +3418,7 @@ static int mlp_bwd_dx_impl(bool w_direct, int R, int N, int K, int ldo, const fl
       if (red->gamma != nullptr)
         a.vfin = BnVecFin{(double)R, red->gamma, red->ss, red->mi, red->vec6, red->dgamma, red->dbeta, sched_slot(),
                           nullptr};
-      if (a.vfin.ticket != nullptr && K <= ACC_MAX_N && env_int("DEMF_ACC_REPL_RED", 0)) a.vfin.racc = accum_slot();
+      if (a.vfin.ticket != nullptr && K <= ACC_MAX_N && sw().acc_repl_red) a.vfin.racc = accum_slot();
       e = G ? launch_gemm<PRO_DY_DENSE, false, false, true>(a, s)
             : launch_gemm<PRO_DY_SPARSE, false, false, true>(a, s);
     } else {
@@ -3455,7 +3426,7 @@ static int mlp_bwd_dx_impl(bool w_direct, int R, int N, int K, int ldo, const fl
     }
     if (e) return e;
   }
-  if (red && red->gamma != nullptr && env_int("DEMF_STATIC_TILES", 0))
+  if (red && red->gamma != nullptr && sw().static_tiles)
     // no counter ring, no last-workgroup ticket: the vectors of layer l-1 as a launch of their own (all K channels)
     return demf_bn_bwd_vectors(K, (long long)R, red->g12, red->gamma, red->ss, red->mi, red->vec6, red->dgamma,
                                red->dbeta, stream);
@@ -3618,32 +3589,31 @@ int dw_plan(int R, int N, int K, int ldx, const float* G, const float* dP, const
   // (round 5: also the 32 768-row products of the vote aggregation - they then join the grouped launch of the other
   // few-row products instead of running as two launches of their own: 292 -> 277 us for the step's 17 products,
   // tools/dw_micro.py; 5.074 -> 5.059 ms per step in situ)
-  static const int small_r = env_int("DEMF_DW_SMALL_R", 65536);
-  if (R <= small_r) tn = tk = 1;
-  static const int tile_ab = env_int("DEMF_DW_TILE", 0);       // A/B: 12 -> 64 x 128 sub-blocks, 21 -> 128 x 64, 22, 11
+  if (R <= sw().dw_small_r) tn = tk = 1;
+  const int tile_ab = sw().dw_tile;       // A/B: 12 -> 64 x 128 sub-blocks, 21 -> 128 x 64, 22, 11
   if (tile_ab) { tn = TNt > 2 ? tile_ab / 10 : 1; tk = TKt > 2 ? tile_ab % 10 : 1; }
   DwArgs a{};
   a.R = R; a.N = N; a.K = K; a.ldx = ldx; a.Yl = Y; a.G = G; a.dP = dP; a.arg = arg; a.ns = ns;
   a.vec = vec6; a.Xp = Xprev; a.pvec = prev_scale_shift; a.dW = dW; a.lddw = lddw;
-  { static const int dbg = env_int("DEMF_DW_DBG", 0); a.dbg = dbg; }
+  a.dbg = sw().dw_dbg;
   const int nsub_n = cdiv(TNt, 2 * tn);
   a.nsub_k = cdiv(TKt, 2 * tk);
   const int nsub = nsub_n * a.nsub_k;
-  static const int x3mask_lds = env_int("DEMF_X3_MASK", 7);
-  const int x3_lds = (compute_bf16() && !env_int("DEMF_DW_F32", 0)) ? 2 : ((compute_mode() == 2 && (x3mask_lds & 4)) ? 1 : 0);
-  if (DEMF_DW_TR && x3_lds != 0)      // bf16 planes [PL][32][W + 8] of both operands (mlp_dw_body)
-    pl.lds = (size_t)(x3_lds == 1 ? 3 : 1) * 32 * ((2 * tn * 32 + 8) + (2 * tk * 32 + 8)) * 2 + sizeof(float) * (5 * N + 2 * K);
+  // (DEMF_X3_MASK bit 2: weight-gradient launches)
+  pl.x3 = (compute_bf16() && !sw().dw_f32) ? 2 : ((compute_mode() == 2 && (sw().x3_mask & 4)) ? 1 : 0);
+  if (DEMF_DW_TR && pl.x3 != 0)      // bf16 planes [PL][32][W + 8] of both operands (mlp_dw_body)
+    pl.lds = (size_t)(pl.x3 == 1 ? 3 : 1) * 32 * ((2 * tn * 32 + 8) + (2 * tk * 32 + 8)) * 2 + sizeof(float) * (5 * N + 2 * K);
   else
     pl.lds = sizeof(float) * (32 * ((2 * tn * 32 + 4) + (2 * tk * 32 + 4)) + 5 * N + 2 * K);
   int gx = cdiv(R, 32 * 4);
-  const int tot = env_int("DEMF_DW_GRID", 512);
+  const int tot = sw().dw_grid;
   const int cap = tot / nsub > 16 ? tot / nsub : 16;
   if (gx > cap) gx = cap;
   if (gx < 1) gx = 1;
   // dynamic chunk claims (DEMF_DW_DYN=1): measured neutral on the training step, so the default
   // stays the static slab striding (chunk = 1)
   a.chunk = 1;
-  if (allow_dyn && env_int("DEMF_DW_DYN", 0)) {
+  if (allow_dyn && sw().dw_dyn) {
     const int nslab = cdiv(R, 32);
     a.chunk = nslab / (gx * 4);                  // >= 4 claims per block, at most DW_CHUNK slabs each
     a.chunk = a.chunk < 1 ? 1 : (a.chunk > DW_CHUNK ? DW_CHUNK : a.chunk);
@@ -3651,9 +3621,7 @@ int dw_plan(int R, int N, int K, int ldx, const float* G, const float* dP, const
     if (gx > nchunk) gx = nchunk;
     if (nchunk > 2 * gx && nsub <= DW_MAX_SUB) a.sched = sched_slot();
   }
-  static const int x3mask = env_int("DEMF_X3_MASK", 7);          // bit 2: weight-gradient launches
   pl.a = a; pl.gx = gx; pl.nsub = nsub; pl.tn = tn; pl.tk = tk; pl.sparse = G == nullptr;
-  pl.x3 = (compute_bf16() && !env_int("DEMF_DW_F32", 0)) ? 2 : ((compute_mode() == 2 && (x3mask & 4)) ? 1 : 0);
   return DEMF_OK;
 }
 
@@ -3710,8 +3678,7 @@ extern "C" int demf_mlp_gemm_bwd_dw_group(int n, const demf_dw_job* jobs, demf_s
                         j.lddw, false, pl))
       return e;
     if (pl.gx) plans.push_back(pl);
-    static const int trace = env_int("DEMF_DW_TRACE", 0);       // the step's products, one line each (tools/dw_micro.py)
-    if (trace && pl.gx)
+    if (sw().dw_trace && pl.gx)       // the step's products, one line each (tools/dw_micro.py)
       fprintf(stderr, "[dw] R=%d N=%d K=%d ldx=%d sparse=%d ns=%d bnrelu_in=%d tile=%dx%d grid=%dx%d\n", j.R, j.N, j.K, j.ldx,
               (int)pl.sparse, j.ns, j.prev_scale_shift != nullptr, pl.tn, pl.tk, pl.gx, pl.nsub);
   }

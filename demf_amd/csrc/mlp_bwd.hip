@@ -1165,26 +1165,18 @@ static int launch_fused(const FusedBwdArgs& a, hipStream_t s) {
   constexpr int P = CM == 2 ? 3 : (CM == 3 ? 2 : 1);
   constexpr int N = NTN * 32, K = KT * 32, NW = NTN * KG;
   const size_t bytes = (size_t)NTN * P * 2 * 2048 + (size_t)P * K * 64 + sizeof(float) * (32 * K + 5 * N + 4 * K + 4 * K + 24);
-  static bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bwd_fused_kernel<NTN, KT, KG, SPARSE, CM, EPI, ST, WIDE>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-      set_error("mlp_bwd_fused: cannot reserve %zu bytes of LDS", bytes);
-      return DEMF_ELAUNCH;
-    }
-    configured = true;
+  static unsigned long long reserved = 0;      // bit per device
+  if (!reserve_lds(reinterpret_cast<const void*>(&mlp_bwd_fused_kernel<NTN, KT, KG, SPARSE, CM, EPI, ST, WIDE>), (int)bytes,
+                   &reserved)) {
+    set_error("mlp_bwd_fused: cannot reserve %zu bytes of LDS", bytes);
+    return DEMF_ELAUNCH;
   }
   const int nslab = (a.R + 31) / 32;
-  // persistent: 8 waves per CU on DEMF_PERSIST_CUS compute units.  Default 240 of 256: the coordinate
+  // persistent: 8 waves per CU on DEMF_PERSIST_CUS_BWD (unset: DEMF_PERSIST_CUS) compute units.  Default 240 of 256: the coordinate
   // pre-pass of the next batch (8 FPS workgroups that each own a CU) is resident underneath the step;
   // a grid sized for all 256 CUs leaves 8 workgroups waiting for a CU and the launch ends with them
   // (measured on the step: 256 -> 6.41 ms, 248 -> 6.35, 240 -> 6.32, 232 -> 6.31, 224 -> 6.33; alone 5.86 either way)
-  static const int cus = [] {
-    const char* b = getenv("DEMF_PERSIST_CUS_BWD");       // the backward kernels alone (A/B)
-    const char* v = b ? b : getenv("DEMF_PERSIST_CUS");
-    return v ? atoi(v) : 240;
-  }();
-  const int cap = cus * (8 / NW);
+  const int cap = sw().persist_cus_bwd * (8 / NW);
   // WIDE: nchunk x (workgroups per chunk) - half as many workgroups per chunk as a launch per chunk would take, each
   // walking twice the slabs: one weight-fragment load, one dW flush (cap / nchunk partials per element) and one drain
   const int gx = WIDE ? a.nchunk * wide_members(nslab, a.nchunk, cap) : (nslab < cap ? nslab : cap);
@@ -1199,8 +1191,7 @@ using namespace demf;
 // A/B switch: DEMF_F16_TERMS_BWD=0 keeps the fused backward kernels on three bf16 terms while the forward kernels
 // take two fp16 terms
 static int fused_h2_mode() {
-  static const int on = [] { const char* v = getenv("DEMF_F16_TERMS_BWD"); return v ? atoi(v) : 1; }();
-  return on;
+  return sw().f16_terms_bwd;
 }
 static bool fused_h2_on() { return fused_h2_mode() != 0; }
 
@@ -1229,7 +1220,7 @@ extern "C" int demf_mlp_bwd_fused(int R, int N, int K, const float* G, const flo
                "mlp_bwd_fused: null pointer");
   set_last_form(DEMF_FORM_FUSED);
   FusedBwdArgs a{};
-  { static const int dbg = getenv("DEMF_BWD_DBG") ? atoi(getenv("DEMF_BWD_DBG")) : 0; a.dbg = dbg; }
+  a.dbg = sw().bwd_dbg;
   a.R = R; a.N = N; a.K = K; a.ns = ns; a.Yl = Y; a.G = G; a.dP = dP; a.arg = arg; a.vec = vec6;
   a.Xp = Yprev; a.pss = scale_shift_prev; a.pmi = mean_invstd_prev; a.W = W; a.dX = dX; a.dW = dW;
   a.g12 = g12_prev; a.fX = X0; a.fsum = first_sums;
@@ -1286,7 +1277,7 @@ extern "C" int demf_mlp_bwd_fused_cols(int R, int N, int Ktot, int c0, int Kc, c
                    g12_prev, "mlp_bwd_fused_cols: null pointer");
   set_last_form(DEMF_FORM_FUSED_COLS);
   FusedBwdArgs a{};
-  { static const int dbg = getenv("DEMF_BWD_DBG") ? atoi(getenv("DEMF_BWD_DBG")) : 0; a.dbg = dbg; }
+  a.dbg = sw().bwd_dbg;
   a.R = R; a.N = N; a.K = Kc; a.ns = ns; a.Yl = Y; a.G = G; a.dP = dP; a.arg = arg; a.vec = vec6;
   a.Xp = Yprev + c0; a.dX = dX + c0; a.W = W + c0; a.dW = dW + c0;
   a.pss = scale_shift_prev; a.pmi = mean_invstd_prev; a.g12 = g12_prev;
@@ -1335,7 +1326,7 @@ extern "C" int demf_mlp_bwd_fused_wide(int R, int N, int Ktot, const float* G, c
                    g12_prev, "mlp_bwd_fused_wide: null pointer");
   set_last_form(DEMF_FORM_FUSED_WIDE);
   FusedBwdArgs a{};
-  { static const int dbg = getenv("DEMF_BWD_DBG") ? atoi(getenv("DEMF_BWD_DBG")) : 0; a.dbg = dbg; }
+  a.dbg = sw().bwd_dbg;
   a.R = R; a.N = N; a.K = Kc; a.ns = ns; a.Yl = Y; a.G = G; a.dP = dP; a.arg = arg; a.vec = vec6;
   a.Xp = Yprev; a.dX = dX; a.W = W; a.dW = dW;
   a.pss = scale_shift_prev; a.pmi = mean_invstd_prev; a.g12 = g12_prev;
@@ -1360,11 +1351,7 @@ extern "C" int demf_mlp_bwd_fused_wide(int R, int N, int Ktot, const float* G, c
 }
 
 static int pool_bwd_grid(int R) {
-  static const int cus = [] {
-    const char* b = getenv("DEMF_PERSIST_CUS_BWD");
-    const char* v = b ? b : getenv("DEMF_PERSIST_CUS");
-    return v ? atoi(v) : 240;
-  }();
+  const int cus = sw().persist_cus_bwd;
   const int nslab = R / PB_RS;
   return nslab < cus ? (nslab > 0 ? nslab : 1) : cus;
 }
@@ -1396,7 +1383,7 @@ extern "C" int demf_mlp_bwd_pool(int R, int N, int K, int ns, const float* dP, c
   PoolBwdArgs a{};
   a.R = R; a.ns = ns; a.Xp = Yprev; a.pss = scale_shift_prev; a.pmi = mean_invstd_prev; a.W = W; a.vec = vec6;
   a.dP = dP; a.arg = arg; a.yraw = yraw; a.dX = dX; a.part = workspace; a.g12 = g12_prev;
-  { static const int dbg = [] { const char* v = getenv("DEMF_PB_DBG"); return v ? atoi(v) : 0; }(); a.dbg = dbg; }
+  a.dbg = sw().pb_dbg;
   if (gamma_prev != nullptr) {
     DEMF_REQUIRE(vec6_prev && dgamma_prev && dbeta_prev, "mlp_bwd_pool: vectors of layer l-1 need all three outputs");
     a.vfin = BnVecFin{(double)R, gamma_prev, scale_shift_prev, mean_invstd_prev, vec6_prev, dgamma_prev,
@@ -1415,17 +1402,14 @@ extern "C" int demf_mlp_bwd_pool(int R, int N, int K, int ns, const float* dP, c
   size_t body = main > scratch ? main : scratch;
   if (body < fold) body = fold;
   const size_t bytes = head + body;
-  static bool configured[4] = {false, false, false, false};
+  static unsigned long long reserved[4] = {0, 0, 0, 0};      // per kernel instantiation: bit per device
   const int var = h2 ? 3 : cm;
-  if (!configured[var]) {
-    const void* fn = var == 1 ? reinterpret_cast<const void*>(&mlp_bwd_pool_kernel<1>)
-                   : (var == 3 ? reinterpret_cast<const void*>(&mlp_bwd_pool_kernel<3>)
-                               : reinterpret_cast<const void*>(&mlp_bwd_pool_kernel<2>));
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-      set_error("mlp_bwd_pool: cannot reserve %zu bytes of LDS", bytes);
-      return DEMF_ELAUNCH;
-    }
-    configured[var] = true;
+  const void* fn = var == 1 ? reinterpret_cast<const void*>(&mlp_bwd_pool_kernel<1>)
+                 : (var == 3 ? reinterpret_cast<const void*>(&mlp_bwd_pool_kernel<3>)
+                             : reinterpret_cast<const void*>(&mlp_bwd_pool_kernel<2>));
+  if (!reserve_lds(fn, (int)bytes, &reserved[var])) {
+    set_error("mlp_bwd_pool: cannot reserve %zu bytes of LDS", bytes);
+    return DEMF_ELAUNCH;
   }
   if (var == 1) hipLaunchKernelGGL(mlp_bwd_pool_kernel<1>, dim3(gx), dim3(512), bytes, s, a);
   else if (var == 3) hipLaunchKernelGGL(mlp_bwd_pool_kernel<3>, dim3(gx), dim3(512), bytes, s, a);
@@ -1450,7 +1434,7 @@ extern "C" int demf_mlp_bwd_fused_x4(int R, int N, int K, const float* G, const 
                "mlp_bwd_fused_x4: null pointer");
   set_last_form(DEMF_FORM_FUSED);
   FusedBwdArgs a{};
-  { static const int dbg = getenv("DEMF_BWD_DBG") ? atoi(getenv("DEMF_BWD_DBG")) : 0; a.dbg = dbg; }
+  a.dbg = sw().bwd_dbg;
   a.R = R; a.N = N; a.K = K; a.ns = 1; a.Yl = Y; a.G = G; a.vec = vec6; a.Xp = nullptr; a.pss = scale_shift_prev;
   a.pmi = mean_invstd_prev; a.W = W; a.dW = dW; a.fX = X0; a.fsum = first_sums; a.W0 = W0;
   a.ldk = K; a.ldw = K; a.fld = K; a.fc0 = 0;

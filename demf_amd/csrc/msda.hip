@@ -17,7 +17,6 @@
 // not an ALU one.  Backward reduces grad_loc / grad_weight across the G lanes with
 // DPP adds (no LDS) and scatters grad_value with hardware fp32 atomics.
 #include "common.h"
-#include <stdlib.h>
 
 namespace demf {
 
@@ -740,8 +739,7 @@ extern "C" int demf_msda_fwd_raw_head_f32(int B, int S, int Q, int P, const floa
                    lds <= 160 * 1024, "msda_fwd_raw_head: levels %d .. 3 = %d tokens do not fit LDS", first_staged_level,
                staged_tokens);
   hipStream_t s = (hipStream_t)stream;
-  static const int target_wgs = getenv("DEMF_MSDA_HEAD_WGS") ? atoi(getenv("DEMF_MSDA_HEAD_WGS")) : 256;   // A/B knob
-  int chunks = (target_wgs + B * 8 - 1) / (B * 8);
+  int chunks = (sw().msda_head_wgs + B * 8 - 1) / (B * 8);   // A/B knob: the workgroups to aim at
   if (chunks < 1) chunks = 1;
   int qpc = ((Q + chunks - 1) / chunks + 8 * MSDA_HW - 1) / (8 * MSDA_HW) * (8 * MSDA_HW);
   chunks = (Q + qpc - 1) / qpc;
@@ -776,12 +774,11 @@ extern "C" int demf_msda_fwd_raw_f32(int B, int S, int H, int Dh, int L, int Q, 
   const long long items = (long long)B * Q * H;
   const dim3 grid((unsigned)((items * 8 + 255) / 256));
   hipStream_t s = (hipStream_t)stream;
-  static const bool lanes8 = getenv("DEMF_MSDA_RAW_LANES") && atoi(getenv("DEMF_MSDA_RAW_LANES"));   // A/B switch
-  if (H == 8 && !lanes8 && ldraw % 2 == 0 && off_col0 % 2 == 0 && (uintptr_t)raw % 8 == 0 && (uintptr_t)ref % 8 == 0) {
+  if (H == 8 && !sw().msda_raw_lanes && ldraw % 2 == 0 && off_col0 % 2 == 0 && (uintptr_t)raw % 8 == 0 && (uintptr_t)ref % 8 == 0) {
     const long long rows = (long long)B * Q;
-    static const int xcd = getenv("DEMF_MSDA_XCD") ? atoi(getenv("DEMF_MSDA_XCD")) : 0;      // A/B switch
+    const int xcd = sw().msda_xcd;      // A/B switch
     const dim3 g2((unsigned)(xcd ? ((rows + 3) / 4 + 7) / 8 * 8 : (rows + 3) / 4));
-    static const int nt = getenv("DEMF_MSDA_NT") ? atoi(getenv("DEMF_MSDA_NT")) : 1;         // A/B switch (12.94 -> 12.65 ms per 6 layers)
+    const int nt = sw().msda_nt;        // A/B switch (12.94 -> 12.65 ms per 6 layers)
 #define RAW_GO(PV, NTV)                                                                                              \
     hipLaunchKernelGGL((msda_fwd_raw_wave_kernel<4, PV, NTV>), g2, dim3(256), 0, s, S, Q, value, vpitch, spatial_shapes, \
                        level_start_index, raw, ldraw, off_col0, lgt_col0, ref, out, rows, xcd)

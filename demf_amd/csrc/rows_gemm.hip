@@ -18,7 +18,6 @@
 // projection: one launch for all three), bias, ReLU, the padding-mask zeroing of value rows, and
 // residual + LayerNorm.  Workgroups are dealt so that all column tiles of a row block run on one XCD.
 #include "common.h"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace demf {
@@ -515,14 +514,10 @@ template <int P>
 static int rows_gemm_ln64_launch(const RowsGemmArgs& a, hipStream_t s) {
   constexpr int stage = P * (64 * 64 + 256 * 64), ln = 64 * 260 * 4;
   constexpr int lds = stage > ln ? stage : ln;
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&rows_gemm_ln64_kernel<P>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-      set_error("rows_gemm: cannot reserve %d bytes of LDS", lds);
-      return DEMF_ELAUNCH;
-    }
-    attr_done = true;
+  static unsigned long long reserved = 0;      // bit per device
+  if (!reserve_lds(reinterpret_cast<const void*>(&rows_gemm_ln64_kernel<P>), lds, &reserved)) {
+    set_error("rows_gemm: cannot reserve %d bytes of LDS", lds);
+    return DEMF_ELAUNCH;
   }
   hipLaunchKernelGGL((rows_gemm_ln64_kernel<P>), dim3(cdiv(a.R, 64)), dim3(512), lds, s, a);
   return check_launch("rows_gemm_ln64_kernel");
@@ -533,14 +528,10 @@ static int rows_gemm_launch(const RowsGemmArgs& a, hipStream_t s) {
   constexpr int bytes = (TWO ? 1 : 2) * P * (RG_BM * 64 + BN * 64);
   constexpr int ln_bytes = BN == 256 ? 128 * 260 * 4 : 0;
   constexpr int lds = bytes > ln_bytes ? bytes : ln_bytes;
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&rows_gemm_kernel<P, BN, TWO>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-      set_error("rows_gemm: cannot reserve %d bytes of LDS", lds);
-      return DEMF_ELAUNCH;
-    }
-    attr_done = true;
+  static unsigned long long reserved = 0;      // bit per device
+  if (!reserve_lds(reinterpret_cast<const void*>(&rows_gemm_kernel<P, BN, TWO>), lds, &reserved)) {
+    set_error("rows_gemm: cannot reserve %d bytes of LDS", lds);
+    return DEMF_ELAUNCH;
   }
   const int gx = a.N / BN, gy = (cdiv(a.R, RG_BM) + 7) / 8 * 8;
   hipLaunchKernelGGL((rows_gemm_kernel<P, BN, TWO>), dim3(gx * gy), dim3(512), lds, s, a);
@@ -566,30 +557,25 @@ extern "C" int demf_rows_gemm_f32(int R, int N, int K, const float* A, long long
   a.W = reinterpret_cast<const __bf16*>(w_planes); a.bias = bias; a.mode = mode;
   a.row_mask = row_mask; a.mask_col0 = mask_col0; a.resid = resid; a.ldr = ldr;
   a.gamma = gamma; a.beta = beta; a.eps = eps; a.C = C; a.ldc = ldc;
-  static const int rg_dbg = getenv("DEMF_RG_DBG") ? atoi(getenv("DEMF_RG_DBG")) : 0;    // phase-skip timing experiments
-  a.dbg = rg_dbg;
+  a.dbg = sw().rg_dbg;    // phase-skip timing experiments
   hipStream_t s = (hipStream_t)stream;
   if (mode == 2) {
     DEMF_REQUIRE(N == 256 && resid != nullptr && gamma != nullptr && beta != nullptr && ldr % 4 == 0 && ldc % 4 == 0,
                  "rows_gemm: the LayerNorm epilogue needs N == 256, a residual and gamma / beta");
-    static const int ln128 = getenv("DEMF_RG_LN128") ? atoi(getenv("DEMF_RG_LN128")) : 0;   // A/B: the 128-row form
-    if (!ln128 && A2 == nullptr) return planes == 3 ? rows_gemm_ln64_launch<3>(a, s) : rows_gemm_ln64_launch<1>(a, s);
+    if (!sw().rg_ln128 && A2 == nullptr) return planes == 3 ? rows_gemm_ln64_launch<3>(a, s) : rows_gemm_ln64_launch<1>(a, s);
     return planes == 3 ? rows_gemm_launch<3, 256, false>(a, s) : rows_gemm_launch<1, 256, false>(a, s);
   }
   DEMF_REQUIRE(N % 128 == 0, "rows_gemm: N %% 128 required (N = %d)", N);
   DEMF_REQUIRE(A2 == nullptr || a2_cols % 128 == 0 || a2_cols >= N, "rows_gemm: a2_cols must be a multiple of 128");
-  static const int w8 = getenv("DEMF_RG_WAVES8") ? atoi(getenv("DEMF_RG_WAVES8")) : 0;    // A/B: the 8-wave forms
-  if (!w8) {
+  if (!sw().rg_waves8) {    // A/B: the 8-wave forms
     // (the adding form needs 16 more staging registers: 116 bytes of scratch at three planes, 631 vs 400 us on the
     // encoder's input projection - it stays on the 8-wave form; callers with a pre-added operand use a2_op = 1)
     if (A2 == nullptr || a2_op == 1)
       return planes == 3 ? rows_gemm4_launch<3, false>(a, s) : rows_gemm4_launch<1, false>(a, s);
-    static const int add4 = getenv("DEMF_RG_ADD4") ? atoi(getenv("DEMF_RG_ADD4")) : 0;      // A/B: adding form on 4 waves
     if (planes == 1) return rows_gemm4_launch<1, true>(a, s);
-    if (add4) return rows_gemm4_launch<3, true>(a, s);
+    if (sw().rg_add4) return rows_gemm4_launch<3, true>(a, s);
   }
-  static const bool one = getenv("DEMF_RG_ONE") && atoi(getenv("DEMF_RG_ONE"));     // A/B: one workgroup per CU
-  if (one) return planes == 3 ? rows_gemm_launch<3, 128, false>(a, s) : rows_gemm_launch<1, 128, false>(a, s);
+  if (sw().rg_one) return planes == 3 ? rows_gemm_launch<3, 128, false>(a, s) : rows_gemm_launch<1, 128, false>(a, s);
   return planes == 3 ? rows_gemm_launch<3, 128, true>(a, s) : rows_gemm_launch<1, 128, true>(a, s);
 }
 

@@ -9,7 +9,6 @@
 // Strict '<' insertion keeps the upstream "earliest source wins ties" order.
 // three_interpolate: 3-tap weighted row gather; HBM/L2-bound.
 #include "common.h"
-#include <stdlib.h>
 
 namespace demf {
 
@@ -277,8 +276,7 @@ static inline int grid_rows(long long rows) {
 using namespace demf;
 
 static bool three_nn_split(int m) {
-  static const int on = [] { const char* v = getenv("DEMF_THREE_NN_SPLIT"); return v ? atoi(v) : 1; }();   // A/B switch
-  return on && m >= 64;
+  return sw().three_nn_split && m >= 64;   // A/B switch
 }
 
 extern "C" int demf_three_nn_f32(int B, int n, int m, const float* target,

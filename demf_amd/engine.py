@@ -18,20 +18,22 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import switches
+
 
 def init_distributed():
     """Reads RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment (torchrun)."""
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    if os.environ.get("DEMF_SHARE_DEVICE"):
+    if switches.env_on("DEMF_SHARE_DEVICE"):
         # test hook: several ranks on ONE GPU (with DEMF_DIST_BACKEND=gloo), to exercise the
         # multi-rank code path of bench.py on a single-GPU box
         local = 0
     if world > 1 and not dist.is_initialized():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29500")
-        backend = os.environ.get("DEMF_DIST_BACKEND") or \
+        backend = switches.env_str("DEMF_DIST_BACKEND") or \
             ("nccl" if torch.cuda.is_available() else "gloo")
         if torch.cuda.is_available():
             torch.cuda.set_device(local)
@@ -570,7 +572,7 @@ class Trainer:
             # (bench.py secondary.allreduce_stub100us_*; profiles/r05_allreduce_overlap_probe.log) the extra
             # cross-queue dependencies of the deferred order cost 0.23 ms per step - more than a 100 us collective
             # takes on the step's own stream
-            ov = bool(int(os.environ.get("DEMF_AR_OVERLAP", "0")))
+            ov = bool(switches.env_int("DEMF_AR_OVERLAP"))
         return world, stub, bool(ov) and (world > 1 or stub > 0)
 
     def _collective(self, world, stub):
@@ -786,7 +788,7 @@ class Trainer:
                 role = "last" if self.micro == W_c - 1 else "accumulate"
             if role not in ("accumulate", "last"):
                 raise ValueError("capture(role=%r): 'accumulate' or 'last'" % (role,))
-            if os.environ.get("DEMF_GEO_AT_BWD"):
+            if switches.env_on("DEMF_GEO_AT_BWD"):
                 raise RuntimeError("DEMF_GEO_AT_BWD=1 (forward and backward as two graphs) is not available with "
                                    "accumulate = %d > 1" % W_c)
             self._refuse_overlap()
@@ -794,9 +796,9 @@ class Trainer:
             dry = True
         world_c, stub_c, _ = self.allreduce_config()
         if update_in_graph is None:
-            update_in_graph = bool(int(os.environ.get("DEMF_GRAPH_UPDATE", "1")))
+            update_in_graph = bool(switches.env_int("DEMF_GRAPH_UPDATE"))
         update_in_graph = bool(update_in_graph) and self.fused and stub_c == 0 and \
-            (world_c == 1 or bool(int(os.environ.get("DEMF_GRAPH_ALLREDUCE", "0"))))
+            (world_c == 1 or bool(switches.env_int("DEMF_GRAPH_ALLREDUCE")))
         gt_list = isinstance(batch["gt_bboxes_3d"], (list, tuple))
         if gt_list and dev.type == "cuda":
             G = max_gt or max(1, max(int((b.tensor if hasattr(b, "tensor") else b).shape[0])
@@ -812,7 +814,7 @@ class Trainer:
         # the 152 MB pyramid into static maps and transposing those inside the graph.
         tok_static = None
         if (not isinstance(feats, dict) and dev.type == "cuda" and hasattr(head, "pyramid_tokens")
-                and int(os.environ.get("DEMF_ZERO_COPY_TOKENS", "1"))):
+                and switches.env_int("DEMF_ZERO_COPY_TOKENS")):
             tok_static = head.pyramid_tokens(feats, batch["img_metas"])
         static = dict(points=batch["points"].clone(),
                       img_features=(tok_static if tok_static is not None else
@@ -858,7 +860,7 @@ class Trainer:
         self.flat.reserve_table()
         graph = torch.cuda.CUDAGraph()
         graph_bwd = None
-        if can_prefetch and os.environ.get("DEMF_GEO_AT_BWD"):
+        if can_prefetch and switches.env_on("DEMF_GEO_AT_BWD"):
             # DEMF_GEO_AT_BWD=1: forward and backward as two graphs (one memory pool) with the pre-pass
             # started in between, underneath the backward (round 2's default: 9.26 -> 9.11 ms/step then).
             # With the one-pass backward kernels of round 3 the backward is ~230 mostly small launches and
@@ -921,7 +923,7 @@ class Trainer:
         # forward).  In the graph, the captured launch holds their addresses; outside, the eager update gets them.
         metered = self.meter is not None
         scalars = self._loss_scalars if metered else None
-        one_deep = not os.environ.get("DEMF_GEO_TWO_DEEP")         # A/B: see replay()
+        one_deep = not switches.env_on("DEMF_GEO_TWO_DEEP")         # A/B: see replay()
 
         def replay(next_points=None):
             """``run`` behind the gradient-accumulation checks: the role this step was captured in must be the one
@@ -966,7 +968,7 @@ class Trainer:
                                        % world_c)
             update = (lambda defer=False: None) if (update_in_graph or role == "accumulate") else \
                 self._update if not metered else (lambda defer=False: self._update(defer, scalars=scalars))
-            if can_prefetch and os.environ.get("DEMF_SKIP_GEO"):     # measurement only: the step alone
+            if can_prefetch and switches.env_on("DEMF_SKIP_GEO"):     # measurement only: the step alone
                 self.flush()
                 graph.replay()
                 if graph_bwd is not None:

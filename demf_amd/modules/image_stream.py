@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import switches
 from ..geometry import level_masks
 from .transformer import FFN, MultiScaleDeformableAttention
 
@@ -31,15 +32,15 @@ from .transformer import FFN, MultiScaleDeformableAttention
 # the encoder layers on csrc/rows_gemm.hip + the raw-input MSDA kernel (embed_dims 256, 8 heads, 4 levels);
 # False / DEMF_ENC_FUSED=0: the module path (ops.linear + torch elementwise), which the golden vectors of the
 # REAL reference encoder pin - the fused path is tested against it
-FUSED_LAYERS = bool(int(__import__("os").environ.get("DEMF_ENC_FUSED", "1")))
-CHANNELS_LAST = bool(int(__import__("os").environ.get("DEMF_IMG_NHWC", "1")))        # A/B switch
+FUSED_LAYERS = bool(switches.env_int("DEMF_ENC_FUSED"))
+CHANNELS_LAST = bool(switches.env_int("DEMF_IMG_NHWC"))        # A/B switch
 # ResNet-50 + ChannelMapper on csrc/conv.hip (implicit-GEMM convolutions on NHWC rows, frozen BatchNorm folded into
 # the pre-split weights, GroupNorm written straight into the token buffer); False / DEMF_IMG_CONV=0: the library
 # convolutions (MIOpen)
-CONV_KERNELS = bool(int(__import__("os").environ.get("DEMF_IMG_CONV", "1")))
-MIOPEN_SEARCH = bool(int(__import__("os").environ.get("DEMF_MIOPEN_SEARCH", "0")))   # library path only
-PRE_ADD = bool(int(__import__("os").environ.get("DEMF_ENC_PRE_ADD", "0")))           # A/B switch (measured neutral: 13.4 vs 13.2 ms)
-SPLIT_FFN_LN = bool(int(__import__("os").environ.get("DEMF_ENC_SPLIT_LN", "1")))     # A/B switch
+CONV_KERNELS = bool(switches.env_int("DEMF_IMG_CONV"))
+MIOPEN_SEARCH = bool(switches.env_int("DEMF_MIOPEN_SEARCH"))   # library path only
+PRE_ADD = bool(switches.env_int("DEMF_ENC_PRE_ADD"))           # A/B switch (measured neutral: 13.4 vs 13.2 ms)
+SPLIT_FFN_LN = bool(switches.env_int("DEMF_ENC_SPLIT_LN"))     # A/B switch
 
 
 class Bottleneck(nn.Module):

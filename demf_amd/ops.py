@@ -7,13 +7,12 @@ raw device pointers + the current HIP stream cross the C ABI.  There is no CPU o
 eager fallback: a CPU tensor or a missing library raises.
 """
 import ctypes
-import os
 
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import _ffi
+from . import _ffi, switches
 
 __all__ = [
     "set_compute_dtype", "get_compute_dtype", "gt_prep", "target_weights", "vote_combine", "furthest_point_sample", "ball_query", "grouping_operation", "gather_points",
@@ -30,7 +29,7 @@ def _stream():
 # F.conv2d for image-stream widths the kernels of csrc/conv.hip do not take - are off the captured hot path (the
 # profile shows no library kernel) and must not be taken silently: they raise unless this is set
 # (DEMF_ALLOW_LIBRARY_FALLBACK=1, or ops.LIBRARY_FALLBACK = True in a test).
-LIBRARY_FALLBACK = bool(int(os.environ.get("DEMF_ALLOW_LIBRARY_FALLBACK", "0") or 0))
+LIBRARY_FALLBACK = bool(switches.env_int("DEMF_ALLOW_LIBRARY_FALLBACK"))
 
 
 def library_fallback(what):
@@ -53,7 +52,7 @@ class _DeferredDW:
 
 
 DEFER = _DeferredDW()
-_DEFER_DW = int(os.environ.get("DEMF_DEFER_DW", "1") or 0)
+_DEFER_DW = switches.env_int("DEMF_DEFER_DW")
 
 
 def _plain_parameter(w):
@@ -217,7 +216,7 @@ _COMPUTE_DTYPE = "f32"
 
 _COMPUTE_MODES = {"f32_native": 0, "bf16": 1, "f32x3": 2, "f32h2": 2}
 # the library's mode (demf_set_compute_dtype); its initial value follows the same environment switch
-_COMPUTE_MODE = 0 if int(os.environ.get("DEMF_F32_NATIVE", "0") or 0) else 2
+_COMPUTE_MODE = 0 if switches.env_nonzero("DEMF_F32_NATIVE") else 2
 
 
 def set_compute_dtype(name):
@@ -238,14 +237,14 @@ def set_compute_dtype(name):
     Process-wide (demf_set_compute_dtype, demf_set_f16_terms)."""
     global _COMPUTE_DTYPE
     if name == "f32":
-        mode = 0 if int(os.environ.get("DEMF_F32_NATIVE", "0") or 0) else 2
+        mode = 0 if switches.env_nonzero("DEMF_F32_NATIVE") else 2
     elif name in _COMPUTE_MODES:
         mode = _COMPUTE_MODES[name]
     else:
         raise ValueError("compute dtype must be 'f32' or one of %s" % sorted(_COMPUTE_MODES))
     _ffi.call("demf_set_compute_dtype", mode)
     if mode == 2:
-        h2 = name == "f32h2" or (name == "f32" and int(os.environ.get("DEMF_F16_TERMS", "1") or 0) != 0)
+        h2 = name == "f32h2" or (name == "f32" and switches.env_int("DEMF_F16_TERMS") != 0)
         _ffi.call("demf_set_f16_terms", int(h2))
     global _COMPUTE_MODE
     _COMPUTE_DTYPE, _COMPUTE_MODE = name, mode
@@ -309,7 +308,7 @@ def furthest_point_sample(points_xyz, num_points):
     return _FurthestPointSampling.apply(points_xyz, num_points)
 
 
-_BQ_GRID_MIN_N = int(os.environ.get("DEMF_BQ_GRID_MIN_N", "8192"))     # smaller clouds: the all-pairs scan
+_BQ_GRID_MIN_N = switches.env_int("DEMF_BQ_GRID_MIN_N")     # smaller clouds: the all-pairs scan
 
 
 class _BallQuery(Function):
@@ -1018,7 +1017,7 @@ def groupnorm_nhwc_into(x, groups, gamma, beta, eps, tokens, row0):
     return tokens
 
 
-_MSDA_HEAD = int(os.environ.get("DEMF_MSDA_HEAD", "1") or 0)        # A/B switch: the (scene, head)-major form
+_MSDA_HEAD = switches.env_int("DEMF_MSDA_HEAD")        # A/B switch: the (scene, head)-major form
 
 
 def msda_fwd_raw(raw, value_col0, off_col0, lgt_col0, ref, spatial_shapes, level_start_index, B, S, H, Dh, P, out,
@@ -1050,15 +1049,15 @@ def msda_fwd_raw(raw, value_col0, off_col0, lgt_col0, ref, spatial_shapes, level
 # Fused shared MLP: (1x1 conv -> train-mode BN -> ReLU) x L [-> max over ns]
 # --------------------------------------------------------------------------
 _ACCUM64 = {}
-_OWN_GEMM_ROWS = int(__import__('os').environ.get('DEMF_OWN_GEMM_ROWS', '65536'))    # A/B switch
-_NO_FPS_CHECK = bool(int(__import__('os').environ.get('DEMF_NO_FPS_CHECK', '0')))       # A/B switch
-_NO_RED_FUSE = bool(int(__import__('os').environ.get('DEMF_NO_RED_FUSE', '0')))        # A/B switch
-_NO_FIRST_FUSE = bool(int(__import__('os').environ.get('DEMF_NO_FIRST_FUSE', '0')))    # A/B switch
-_NO_BWD_FUSE = bool(int(__import__('os').environ.get('DEMF_NO_BWD_FUSE', '0')))        # A/B switch
+_OWN_GEMM_ROWS = switches.env_int("DEMF_OWN_GEMM_ROWS")       # A/B switch
+_NO_FPS_CHECK = bool(switches.env_int("DEMF_NO_FPS_CHECK"))   # A/B switch
+_NO_RED_FUSE = bool(switches.env_int("DEMF_NO_RED_FUSE"))     # A/B switch
+_NO_FIRST_FUSE = bool(switches.env_int("DEMF_NO_FIRST_FUSE")) # A/B switch
+_NO_BWD_FUSE = bool(switches.env_int("DEMF_NO_BWD_FUSE"))     # A/B switch
 # bf16 ROW storage of SA1's stack in the bf16 compute mode: built and parity-tested, measured neutral on
 # the step (5.26 vs 5.23 ms: these kernels are not HBM-bound), so opt-in (DEMF_BF16_STORE=1)
-_NO_BF16_STORE = not bool(int(__import__('os').environ.get('DEMF_BF16_STORE', '0')))
-_VEC_FIN = int(__import__('os').environ.get('DEMF_VEC_FIN', '7'))   # A/B: bit 0 sparse reduce, 1 fused, 2 dx_red
+_NO_BF16_STORE = not switches.env_int("DEMF_BF16_STORE")
+_VEC_FIN = switches.env_int("DEMF_VEC_FIN")   # A/B: bit 0 sparse reduce, 1 fused, 2 dx_red
 
 
 def _bwd_fused_ok(N, K, ns, sparse, first=False):
@@ -1074,7 +1073,7 @@ def _bwd_fused_ok(N, K, ns, sparse, first=False):
 # rows from which a 256-output layer with a 256 / 384 / 512-channel input takes the one-pass backward per
 # 128-column chunk; 0 = never (default: measured neutral on the step - 5.67 vs 5.67 ms - because the
 # (256,128) kernel walks a 32-row slab in ~8 us and the vote aggregation's 32 768 rows are 4 slabs per block)
-_FUSED_COLS_MIN_R = int(os.environ.get("DEMF_FUSED_COLS_MIN_R", "0"))
+_FUSED_COLS_MIN_R = switches.env_int("DEMF_FUSED_COLS_MIN_R")
 
 
 def _bwd_fused_cols_ok(R, N, K, ns, sparse):
@@ -1090,7 +1089,7 @@ def _bwd_fused_cols_ok(R, N, K, ns, sparse):
 
 # rows from which such a layer takes the one-pass backward as ONE launch over all its 128-column chunks
 # (demf_mlp_bwd_fused_wide, csrc/mlp_bwd.hip); 0 = never.  DEMF_FUSED_COLS_MIN_R > 0 takes precedence (A/B).
-_FUSED_WIDE_MIN_R = int(os.environ.get("DEMF_FUSED_WIDE_MIN_R", "16384"))
+_FUSED_WIDE_MIN_R = switches.env_int("DEMF_FUSED_WIDE_MIN_R")
 
 
 def _bwd_fused_wide_ok(R, N, K, ns, sparse):
@@ -1105,26 +1104,25 @@ def _bwd_fused_wide_ok(R, N, K, ns, sparse):
 
 # SA1's pooled last layer without its (R x 128) output: the forward does not store it, the backward is
 # written in terms of the layer's INPUT activations (csrc/mlp_bwd.hip mlp_bwd_pool_kernel).  A/B switch.
-_POOL_NOY = bool(int(os.environ.get("DEMF_POOL_NOY", "1")))
+_POOL_NOY = bool(switches.env_int("DEMF_POOL_NOY"))
 
 
 # SA1's first layer (4-float rows -> 64 channels) without its (R x 64) output: statistics from the rows'
 # second moments, the consumers rebuild the values they need (csrc/mlp.hip mlp_first_stats_k, ST bit 3 of
 # mlp_fwd_res_kernel; csrc/mlp_bwd.hip ST bit 2).  A/B switch.
-_SA1_X4 = bool(int(os.environ.get("DEMF_SA1_X4", "1")))
+_SA1_X4 = bool(switches.env_int("DEMF_SA1_X4"))
 
 
 def _x3_forward_on():
     """The no-store forwards exist in the bf16 / three-term kernels only: in mode 2 the A/B switch DEMF_X3_MASK
     without bit 0 sends forward launches to the native-fp32 kernel (csrc/mlp.hip launch_gemm), which stores."""
-    return _COMPUTE_MODE == 1 or (_COMPUTE_MODE == 2 and (int(os.environ.get("DEMF_X3_MASK", "7") or 0) & 1))
+    return _COMPUTE_MODE == 1 or (_COMPUTE_MODE == 2 and (switches.lib("DEMF_X3_MASK") & 1))
 
 
 def _sa1_x4_ok(R, ld, shapes, training, x_grad, ns):
     return (_SA1_X4 and training and not x_grad and _x3_forward_on() and ld == 4 and len(shapes) >= 3
             and shapes[0] == (64, 4) and shapes[1] == (64, 64) and R >= 16384 and not _NO_BWD_FUSE
-            and not _NO_FIRST_FUSE and int(os.environ.get("DEMF_FWD_RES", "1") or 0) and
-            not int(os.environ.get("DEMF_STATIC_TILES", "0") or 0))
+            and not _NO_FIRST_FUSE and switches.lib("DEMF_FWD_RES") and not switches.lib("DEMF_STATIC_TILES"))
 
 
 def _pool_noy_ok(R, ns, shapes, training, fuse_pool):
@@ -1135,8 +1133,8 @@ def _pool_noy_ok(R, ns, shapes, training, fuse_pool):
             and not _NO_BWD_FUSE and (_VEC_FIN & 1))
 
 
-_NO_GROUP_FIRST = bool(int(__import__('os').environ.get('DEMF_NO_GROUP_FIRST', '0')))  # A/B switch
-_NO_FUSED_POOL = bool(int(__import__('os').environ.get('DEMF_NO_FUSED_POOL', '0')))   # A/B switch
+_NO_GROUP_FIRST = bool(switches.env_int("DEMF_NO_GROUP_FIRST"))  # A/B switch
+_NO_FUSED_POOL = bool(switches.env_int("DEMF_NO_FUSED_POOL"))    # A/B switch
 
 
 def _accum64(n, device):

@@ -516,6 +516,11 @@ DEMF_INTERNAL int demf_mlp_bwd_fused_wide(int R, int N, int Ktot, const float* G
 #define DEMF_FORM_POOL 8        /* mlp_bwd_pool_kernel (demf_mlp_bwd_pool) */
 DEMF_INTERNAL int demf_mlp_last_form(void);
 
+/* The library's A/B switches (csrc/switches.h), read from the environment ONCE per process at the first call that
+ * needs one.  Entry ``index`` of the table: its environment name, the value this process runs with and the default
+ * (any of the three pointers may be NULL).  DEMF_EINVAL past the end; no device work. */
+DEMF_INTERNAL int demf_switch_at(int index, const char** name, int* value, int* dflt);
+
 /* SA1-shaped stacks (4-float grouped rows -> N0 <= 64 channels -> ...): the first layer WITHOUT its (R x N0)
  * output.  y = x.W0^T is linear in the 16-byte row, so
  *   demf_mlp_first_stats      the layer's train-mode BN statistics + bookkeeping from the 14 second moments of the

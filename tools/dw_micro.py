@@ -4,7 +4,7 @@ Phase-skip bits DEMF_DW_DBG need a library built with -DDEMF_DW_PROFILE.  Knobs:
 import os, sys, ctypes
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from demf_amd import _ffi, ops
+from demf_amd import _ffi, ops, switches
 ops.set_compute_dtype(os.environ.get("MODE", "f32"))
 p = lambda t: None if t is None else t.data_ptr()
 # (R, N, K, sparse, ns, bnrelu_in, count per step)
@@ -43,4 +43,4 @@ for j, f in zip(jobs, flops):
 arr = (_ffi.DwJob * len(jobs))(*jobs)
 g = timeit(lambda: _ffi.call("demf_mlp_gemm_bwd_dw_group", len(jobs), ctypes.addressof(arr), st))
 print("grid %s small_r %s: sum of single launches %.1f us; one grouped call %.1f us (%.1f TF/s)" % (
-    os.environ.get("DEMF_DW_GRID", "512"), os.environ.get("DEMF_DW_SMALL_R", "16384"), tot, g, sum(flops) / g * 1e-6))
+    switches.lib("DEMF_DW_GRID"), switches.lib("DEMF_DW_SMALL_R"), tot, g, sum(flops) / g * 1e-6))

@@ -7,6 +7,7 @@ sys.path.insert(0, ROOT_); sys.path.insert(0, os.path.join(ROOT_, "tests"))
 import numpy as np, torch
 import parity_tools as P
 import test_gpu_parity_full as T
+from demf_amd import switches
 from demf_amd.modules import DeMFHotPath
 cfg = T._cfg(); B = 8
 state = T.conditioned_state()
@@ -30,5 +31,5 @@ for it in range(int(sys.argv[1]) if len(sys.argv) > 1 else 30):
         worst = max(worst, (e, n))
     res.append(worst)
 vals = sorted(r[0] for r in res)
-print("TILE=%s: %d repeats on ONE state: worst weight-gradient rel-L2 min %.2e median %.2e max %.2e" % (os.environ.get("DEMF_FWD_TILE","1"), len(vals), vals[0], vals[len(vals)//2], vals[-1]))
+print("TILE=%s: %d repeats on ONE state: worst weight-gradient rel-L2 min %.2e median %.2e max %.2e" % (switches.lib("DEMF_FWD_TILE"), len(vals), vals[0], vals[len(vals)//2], vals[-1]))
 print(sorted(res, key=lambda r: -r[0])[:4])

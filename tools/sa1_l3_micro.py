@@ -4,7 +4,7 @@ DEMF_MODE=f32|f32_native|f32x3|bf16 the compute mode.
 Used under rocprofv3 --pmc for pipe-utilisation counters."""
 import sys, os, torch
 R_ = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R_)
-from demf_amd import _ffi, ops
+from demf_amd import _ffi, ops, switches
 ops.set_compute_dtype(os.environ.get("DEMF_MODE", "f32"))
 R, K, N, ns = 8 * 2048 * 64, 64, 128, 64
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 20
@@ -33,4 +33,4 @@ s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True
 s.record()
 for _ in range(n): run()
 e.record(); torch.cuda.synchronize()
-print("DEMF_MODE=%s DEMF_VARIANT=%s DEMF_FWD_RES=%s  avg %.1f us" % (os.environ.get("DEMF_MODE", "f32"), VARIANT, os.environ.get("DEMF_FWD_RES", "1"), s.elapsed_time(e) * 1e3 / n))
+print("DEMF_MODE=%s DEMF_VARIANT=%s DEMF_FWD_RES=%s  avg %.1f us" % (os.environ.get("DEMF_MODE", "f32"), VARIANT, switches.lib("DEMF_FWD_RES"), s.elapsed_time(e) * 1e3 / n))
