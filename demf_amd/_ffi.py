@@ -62,6 +62,7 @@ SIGNATURES = {
     "demf_points_floor": [_c_int, _c_int, ctypes.c_longlong] + [_ptr] * 4,
     "demf_points_prep": [_c_int] * 3 + [ctypes.c_longlong] + [_ptr] * 8,
     "demf_image_prep": [_c_int] * 3 + [ctypes.c_longlong] + [_ptr] * 6,
+    "demf_depth_to_points": [_c_int, ctypes.c_longlong, ctypes.c_longlong, _c_int] + [_ptr] * 6 + [_c_int] + [_ptr] * 4,
     "demf_proposal_targets": [_c_int] * 4 + [_c_float] * 3 + [_ptr] * 18,
     "demf_gt_prep": [_c_int] * 3 + [_ptr] * 10,
     "demf_pad_gt": [_c_int] * 2 + [_ptr] * 8,

@@ -41,6 +41,78 @@ def upright_to_bottom_center(boxes):
     return b
 
 
+def read_sunrgbd_calib(path):
+    """Upstream's ``calib/*.txt`` of a SUN RGB-D scene: line 1 the tilt matrix Rt, line 2 the intrinsics K, each 9
+    values in column-major order [dep-recall].  -> dict(K (3,3), Rt (3,3)) float64, row-major as everywhere here."""
+    with open(path) as f:
+        lines = [l for l in f.read().splitlines() if l.strip()]
+    if len(lines) < 2:
+        raise ValueError(f"{path}: expected two lines (Rt, K), got {len(lines)}")
+    mats = []
+    for name, line in zip(("Rt", "K"), lines[:2]):
+        vals = [float(v) for v in line.split()]
+        if len(vals) != 9:
+            raise ValueError(f"{path}: {name} has {len(vals)} values, expected 9")
+        mats.append(np.array(vals, np.float64).reshape(3, 3).T)     # column-major on disk
+    return dict(K=mats[1], Rt=mats[0])
+
+
+class RGBDFrames:
+    """Raw RGB-D frames - a colour image, a registered 16-bit depth PNG and a calibration each - for
+    ``pipeline.FramePipeline``.  No annotations.
+
+    ``frames``: a list of dicts ``{"id", "image", "depth", "K" (9 floats), "Rt" (9 floats)}`` or the path of a JSON
+    file holding such a list (absolute or relative to ``data_root``); image and depth paths are relative to
+    ``data_root``, K and Rt row-major.  ``shift`` / ``depth_scale`` / ``z_max`` / ``pixel_origin``: how a depth word
+    becomes metres and which pixel grid the intrinsics refer to (see ``ops.depth_to_points``); the defaults are SUN
+    RGB-D's storage (words rotated left by 3, millimetres, far readings clamped to 8 m) [dep-recall] with a 0-based
+    pixel grid, which is the one ``depth2img`` projects onto."""
+
+    CLASSES = SUNRGBD_CLASSES
+
+    def __init__(self, data_root, frames, shift=3, depth_scale=1000.0, z_max=8.0, pixel_origin=0.0):
+        import json
+        self.data_root = str(data_root)
+        if isinstance(frames, (str, os.PathLike)):
+            path = str(frames) if os.path.isabs(str(frames)) else os.path.join(self.data_root, str(frames))
+            with open(path) as f:
+                frames = json.load(f)
+        if not isinstance(frames, (list, tuple)):
+            raise ValueError(f"expected a list of frame dicts, got {type(frames).__name__}")
+        if not 0 <= int(shift) <= 15:
+            raise ValueError(f"shift must be in 0..15, got {shift}")
+        if not (float(depth_scale) > 0 and float(z_max) > 0):
+            raise ValueError("depth_scale and z_max must be positive")
+        self.shift, self.depth_scale, self.z_max = int(shift), float(depth_scale), float(z_max)
+        self.pixel_origin = float(pixel_origin)
+        self.frames = []
+        for i, fr in enumerate(frames):
+            missing = [k for k in ("image", "depth", "K", "Rt") if k not in fr]
+            if missing:
+                raise ValueError(f"frame {i}: missing {missing}")
+            K, Rt = np.asarray(fr["K"], np.float64), np.asarray(fr["Rt"], np.float64)
+            if K.size != 9 or Rt.size != 9:
+                raise ValueError(f"frame {i}: K and Rt must hold 9 values each, got {K.size} and {Rt.size}")
+            self.frames.append(dict(id=fr.get("id", i), image=str(fr["image"]), depth=str(fr["depth"]),
+                                    K=K.reshape(3, 3), Rt=Rt.reshape(3, 3)))
+
+    def __len__(self):
+        return len(self.frames)
+
+    def calib_row(self, calib):
+        """-> the (16,) fp64 row of ``ops.depth_to_points``."""
+        K, Rt = calib["K"], calib["Rt"]
+        return np.concatenate([[K[0, 0], K[1, 1], K[0, 2], K[1, 2]], Rt.reshape(9),
+                               [self.pixel_origin, self.depth_scale, self.z_max]]).astype(np.float64)
+
+    def get_data_info(self, index):
+        """-> dict(sample_idx, img_filename, depth_filename, calib (K, Rt), depth2img (3,3) fp32)."""
+        fr = self.frames[index]
+        return dict(sample_idx=fr["id"], img_filename=os.path.join(self.data_root, fr["image"]),
+                    depth_filename=os.path.join(self.data_root, fr["depth"]),
+                    calib=dict(K=fr["K"], Rt=fr["Rt"]), depth2img=depth2img_from_calib(fr["K"], fr["Rt"]))
+
+
 class SUNRGBDDataset:
     """mmdet3d SUNRGBDDataset (modality: points + image) over an infos file.
 

@@ -2,6 +2,10 @@
 
   python -m demf_amd.infer --data-root R --ann-file sunrgbd_infos_val.pkl --checkpoint C
                            [--batch-size 8] [--workers 8] [--out results.pkl] [--no-eval]
+  python -m demf_amd.infer --data-root R --frames manifest.json --checkpoint C --out results.pkl
+
+``--frames`` runs raw RGB-D frames (``dataset.RGBDFrames``: colour image, 16-bit depth PNG, calibration) through
+``pipeline.FramePipeline``; they carry no ground truth, so nothing is evaluated and ``--out`` is required.
 
 ``run_test`` feeds a dataset through ``SceneLoader(mode="test")`` and ``DeMFVoteNet.predict_into``; the
 detections of every scene stay on the device in one ``DetectionStore`` and nothing in the loop waits for the
@@ -19,11 +23,13 @@ from .pipeline import SceneLoader
 
 
 def run_test(model, dataset, batch_size=8, workers=8, num_points=20000, img_scale=(1333, 800), seed=0,
-             store=None):
+             store=None, pipeline=None):
     """Detections of every scene of ``dataset`` in dataset order -> the ``DetectionStore`` holding them (``store``,
-    or a new worst-case one).  The last batch may be smaller; there is no host sync inside the loop."""
+    or a new worst-case one).  The last batch may be smaller; there is no host sync inside the loop.  ``pipeline``:
+    a test-mode pipeline instance for the loader to use (``FramePipeline`` for raw frames), which then brings its
+    own ``num_points`` / ``img_scale`` / ``seed``."""
     loader = SceneLoader(dataset, batch_size, "test", seed=seed, img_scale=img_scale, num_points=num_points,
-                         workers=workers)
+                         workers=workers, pipeline=pipeline)
     model.eval()
     if store is None:
         store = DetectionStore(max(len(dataset), 1), device=loader.device)
@@ -56,7 +62,10 @@ def load_checkpoint(model, path):
 def parse_args(argv=None):
     p = argparse.ArgumentParser(prog="python -m demf_amd.infer", description=__doc__.split("\n")[0])
     p.add_argument("--data-root", required=True)
-    p.add_argument("--ann-file", required=True, help="infos file, absolute or relative to --data-root")
+    src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument("--ann-file", help="infos file, absolute or relative to --data-root")
+    src.add_argument("--frames", help="JSON manifest of raw RGB-D frames, absolute or relative to --data-root; "
+                                      "no ground truth: implies --no-eval and needs --out")
     p.add_argument("--checkpoint", required=True)
     p.add_argument("--batch-size", type=int, default=8)
     p.add_argument("--workers", type=int, default=8)
@@ -65,6 +74,10 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.batch_size < 1 or args.workers < 1:
         p.error("--batch-size and --workers must be positive")
+    if args.frames:
+        args.no_eval = True
+        if not args.out:
+            p.error("--frames has no ground truth to evaluate against: --out is required")
     if args.no_eval and not args.out:
         p.error("--no-eval without --out would discard the detections")
     return args
@@ -75,8 +88,14 @@ def main(argv=None, model=None, **loader_kwargs):
     detector to use instead of the full-size ``DeMFVoteNet()``; ``loader_kwargs`` go to ``run_test``
     (``num_points``, ``img_scale``, ``seed``)."""
     args = parse_args(argv)
-    from .dataset import SUNRGBDDataset
-    dataset = SUNRGBDDataset(args.data_root, args.ann_file, test_mode=True)
+    from .dataset import RGBDFrames, SUNRGBDDataset
+    if args.frames:
+        from .pipeline import FramePipeline
+        dataset = RGBDFrames(args.data_root, args.frames)
+        loader_kwargs["pipeline"] = FramePipeline(dataset, **{k: loader_kwargs.pop(k) for k in
+                                                             ("num_points", "img_scale", "seed") if k in loader_kwargs})
+    else:
+        dataset = SUNRGBDDataset(args.data_root, args.ann_file, test_mode=True)
     if model is None:
         from .modules import DeMFVoteNet
         model = DeMFVoteNet()

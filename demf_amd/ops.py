@@ -2212,6 +2212,54 @@ def image_prep(src, offsets, shapes, pad_shape, mean=IMG_NORM[0], std=IMG_NORM[1
     return out
 
 
+# --------------------------------------------------------------------------
+# RGB-D frame front end (csrc/frame.hip): depth + colour + calibration -> the raw records of the input pipeline
+# --------------------------------------------------------------------------
+FRAME_TILE = 1024                 # pixels per workgroup: kFrameTile of csrc/frame.hip (the entry point checks it)
+
+
+def depth_to_points(depth, depth_off, rgb, rgb_off, shapes, calib, shift=3, out=None):
+    """Unproject B ragged RGB-D frames into point records (see demf_depth_to_points): depth (pixels,) uint16 = the
+    frames' row-major depth images concatenated, depth_off (B+1,) int64 pixel offsets, rgb (bytes,) uint8 / rgb_off
+    (B+1,) int64 / shapes (B,4) int32 as ``image_prep`` takes them (h, w in the first two columns), calib (B,16)
+    fp64 = [fx, fy, cx, cy, Rt row-major (9), pixel_origin, depth_scale, z_max]; ``shift``: the depth words are
+    rotated right by that many bits first (SUN RGB-D stores them rotated left by 3 [dep-recall]; 0 for plain
+    millimetres).  -> raw (pixels, 6) fp32 with the valid pixels' records in front, offsets (B+1,) int64 on the
+    device: what ``points_floor`` / ``points_prep`` take.  Rows at or beyond offsets[B] are not written; the valid
+    counts never come to the host."""
+    _chk(depth, "depth", torch.uint16)
+    _chk(depth_off, "depth_off", torch.int64)
+    _chk(rgb, "rgb", torch.uint8)
+    _chk(rgb_off, "rgb_off", torch.int64)
+    _chk(shapes, "shapes", torch.int32)
+    _chk(calib, "calib", torch.float64)
+    if depth.dim() != 1 or not 0 < depth.numel() < 2 ** 31:
+        raise ValueError(f"depth must be a flat uint16 buffer of 0 < pixels < 2^31, got {tuple(depth.shape)}")
+    if rgb.dim() != 1 or rgb.numel() == 0:
+        raise ValueError(f"rgb must be a non-empty flat uint8 buffer, got {tuple(rgb.shape)}")
+    B = depth_off.numel() - 1
+    if depth_off.dim() != 1 or B < 1 or rgb_off.shape != (B + 1,) or shapes.shape != (B, 4) or calib.shape != (B, 16):
+        raise ValueError(f"depth_off and rgb_off (B+1,) with B >= 1, shapes (B,4), calib (B,16), got "
+                         f"{tuple(depth_off.shape)}, {tuple(rgb_off.shape)}, {tuple(shapes.shape)}, "
+                         f"{tuple(calib.shape)}")
+    if not 0 <= int(shift) <= 15:
+        raise ValueError(f"shift must be in 0..15, got {shift}")
+    total = depth.numel()
+    if out is None:
+        out = torch.empty((total, 6), dtype=torch.float32, device=depth.device)
+    _chk(out, "out")
+    if out.shape != (total, 6):
+        raise ValueError(f"out must be {(total, 6)}, got {tuple(out.shape)}")
+    if any(t.device != depth.device for t in (depth_off, rgb, rgb_off, shapes, calib, out)):
+        raise ValueError("all tensors must be on the same device")
+    ntiles = -(-total // FRAME_TILE)
+    counts = torch.empty((ntiles,), dtype=torch.int32, device=depth.device)
+    offsets = torch.empty((B + 1,), dtype=torch.int64, device=depth.device)
+    _ffi.call("demf_depth_to_points", B, total, rgb.numel(), int(shift), _p(depth), _p(depth_off), _p(rgb),
+              _p(rgb_off), _p(shapes), _p(calib), ntiles, _p(counts), _p(out), _p(offsets), _stream())
+    return out, offsets
+
+
 def sa_index_chain(N, level_indices):
     """[arange(N) per scene] + every SA level's samples as int64 indices into the input cloud (the
     ``sa_indices`` of PointNet2SASSG.forward) from the levels' int32 FPS indices, one launch."""

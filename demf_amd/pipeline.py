@@ -13,6 +13,9 @@ BGR swap is needed for ``to_rgb``) in a thread pool, draws the per-scene random 
 pinned buffers.  The raw records and uint8 pixels are uploaded as they are and csrc/pipeline.hip does the rest on the
 loader's own stream: the floor percentile, the sample + augmentation, and the resize + normalise + pad.
 
+``FramePipeline`` is the same pipeline in test mode with another point source: instead of the ``.bin`` of the offline
+export it uploads a raw frame's 16-bit depth image and csrc/frame.hip unprojects it into the records on the device.
+
 Random draws: one ``numpy.random.Generator`` per scene draws flip, angle, scale, translation in ``data.augment_3d``'s
 order (``draw_aug_params``), then the 64-bit key of the point sample.  So ``augment_3d(pts, boxes, meta,
 default_rng(s))`` and ``draw_aug_params(default_rng(s))`` apply the same transform; the boxes and metadata are
@@ -115,20 +118,20 @@ class ScenePipeline:
         key = [self.seed, epoch, int(index)] if self.mode == "train" else [self.seed, int(index)]
         return np.random.default_rng(key)
 
-    def load(self, index, epoch=0):
-        """Host part of one scene: file reads, JPEG decode, random draws, boxes and metadata."""
+    @staticmethod
+    def read_image(path):
         from PIL import Image
-        info = self.dataset.get_data_info(index)
-        raw = np.fromfile(info["pts_filename"], dtype=np.float32)
-        if raw.size == 0 or raw.size % LOAD_DIM:
-            raise ValueError(f"{info['pts_filename']}: {raw.size} floats is not a positive multiple of {LOAD_DIM}")
-        with Image.open(info["img_filename"]) as im:
-            img = np.asarray(im.convert("RGB"), dtype=np.uint8)
+        with Image.open(path) as im:
+            return np.asarray(im.convert("RGB"), dtype=np.uint8)
+
+    def _scene(self, index, epoch, info, img, source_meta, **source):
+        """What ``load`` returns, from a decoded image and the point source's own entries: random draws, boxes and
+        metadata."""
         h, w = img.shape[:2]
         rng = self.scene_rng(index, epoch)
         params = draw_aug_params(rng) if self.mode == "train" else identity_aug_params()
         seed = int(rng.integers(0, 2 ** 63 - 1))
-        meta = dict(sample_idx=info["sample_idx"], pts_filename=info["pts_filename"],
+        meta = dict(sample_idx=info["sample_idx"], **source_meta,
                     img_filename=info["img_filename"], depth2img=info["depth2img"], flip=False,
                     img_norm_cfg=dict(mean=np.asarray(self.img_norm[0], np.float32),
                                       std=np.asarray(self.img_norm[1], np.float32), to_rgb=True))
@@ -137,59 +140,133 @@ class ScenePipeline:
         ann = info.get("ann_info")
         boxes = ann["gt_bboxes_3d"] if ann is not None else np.zeros((0, 7), np.float32)
         boxes, meta = apply_aug_params(boxes, meta, params)
-        return dict(index=int(index), raw=raw.reshape(-1, LOAD_DIM), img=img, params=params, seed=seed, meta=meta,
-                    gt_bboxes_3d=boxes, gt_labels_3d=None if ann is None else ann["gt_labels_3d"])
+        return dict(index=int(index), img=img, params=params, seed=seed, meta=meta, gt_bboxes_3d=boxes,
+                    gt_labels_3d=None if ann is None else ann["gt_labels_3d"], **source)
+
+    def load(self, index, epoch=0):
+        """Host part of one scene: file reads, JPEG decode, random draws, boxes and metadata."""
+        info = self.dataset.get_data_info(index)
+        raw = np.fromfile(info["pts_filename"], dtype=np.float32)
+        if raw.size == 0 or raw.size % LOAD_DIM:
+            raise ValueError(f"{info['pts_filename']}: {raw.size} floats is not a positive multiple of {LOAD_DIM}")
+        return self._scene(index, epoch, info, self.read_image(info["img_filename"]),
+                           dict(pts_filename=info["pts_filename"]), raw=raw.reshape(-1, LOAD_DIM))
+
+    # ---- the point source: what is uploaded for the clouds and how it becomes (raw, offsets) on the device ----------
+    def pack_source(self, scenes):
+        """-> (pinned buffers uploaded as they are, small host arrays that travel in the batch's one small upload)."""
+        npts = np.array([s["raw"].shape[0] for s in scenes], np.int64)
+        raw_h = torch.empty((int(npts.sum()), LOAD_DIM), dtype=torch.float32, pin_memory=True)
+        raw_np = raw_h.numpy()
+        poff = np.concatenate([[0], np.cumsum(npts)]).astype(np.int64)
+        for b, s in enumerate(scenes):
+            raw_np[poff[b]:poff[b + 1]] = s["raw"]
+        return dict(raw=raw_h), dict(poff=poff)
+
+    def source_records(self, big, small, img_d):
+        """On the pipeline's stream: the uploaded buffers -> (raw (total, 6) records, offsets (B+1,) int64)."""
+        return big["raw"], small["poff"]
 
     def to_device(self, scenes, device, stream=None):
-        """Pack ``load`` results into pinned buffers, upload them and run the three kernels on ``stream`` (default:
+        """Pack ``load`` results into pinned buffers, upload them and run the kernels on ``stream`` (default:
         the current stream).  -> (batch dict, uploaded bytes).  The batch is valid on ``stream`` once the call
         returns; another stream must wait on it first."""
         B = len(scenes)
-        npts = np.array([s["raw"].shape[0] for s in scenes], np.int64)
         nbytes = np.array([s["img"].size for s in scenes], np.int64)
-        raw_h = torch.empty((int(npts.sum()), LOAD_DIM), dtype=torch.float32, pin_memory=True)
         img_h = torch.empty((int(nbytes.sum()),), dtype=torch.uint8, pin_memory=True)
-        raw_np, img_np = raw_h.numpy(), img_h.numpy()
-        poff = np.concatenate([[0], np.cumsum(npts)]).astype(np.int64)
+        img_np = img_h.numpy()
         ioff = np.concatenate([[0], np.cumsum(nbytes)]).astype(np.int64)
         for b, s in enumerate(scenes):
-            raw_np[poff[b]:poff[b + 1]] = s["raw"]
             img_np[ioff[b]:ioff[b + 1]] = s["img"].reshape(-1)
-        small = torch.empty((B * 4 + 2 * (B + 1) + B + 2 * B,), dtype=torch.int64, pin_memory=True)
-        sm = small.numpy()
-        sm[:B * 4].view(np.float32)[:] = np.stack([param_row(s["params"]) for s in scenes]).reshape(-1)
-        o = B * 4
-        sm[o:o + B + 1] = poff
-        sm[o + B + 1:o + 2 * B + 2] = ioff
-        sm[o + 2 * B + 2:o + 3 * B + 2] = [s["seed"] for s in scenes]
         shp = []
         for s in scenes:
             h, w = s["img"].shape[:2]
             nh, nw = s["meta"]["img_shape"][:2]
             shp += [h, w, nh, nw]
-        sm[o + 3 * B + 2:o + 3 * B + 2 + 2 * B].view(np.int32)[:] = shp
+        big, words = self.pack_source(scenes)
+        # every small array as whole 8-byte words of one upload: params (B,8) fp32, the source's, offsets, seeds, shapes
+        words = dict(params=np.stack([param_row(s["params"]) for s in scenes]).reshape(-1), **words, ioff=ioff,
+                     seeds=np.array([s["seed"] for s in scenes], np.int64), shapes=np.array(shp, np.int32))
+        words = {k: np.ascontiguousarray(v).reshape(-1) for k, v in words.items()}
+        at, n = {}, 0
+        for k, v in words.items():
+            if v.nbytes % 8:
+                raise ValueError(f"{k}: {v.nbytes} bytes is not a whole number of 8-byte words")
+            at[k] = (n, n + v.nbytes // 8)
+            n += v.nbytes // 8
+        small = torch.empty((n,), dtype=torch.int64, pin_memory=True)
+        sm = small.numpy()
+        for k, v in words.items():
+            sm[at[k][0]:at[k][1]].view(v.dtype)[:] = v
         (Hp, Wp), metas = collate_metas([s["meta"] for s in scenes], self.pad_divisor)
         stream = torch.cuda.current_stream(device) if stream is None else stream
         with torch.cuda.stream(stream):
-            raw_d = raw_h.to(device, non_blocking=True)
+            big_d = {k: t.to(device, non_blocking=True) for k, t in big.items()}
             img_d = img_h.to(device, non_blocking=True)
             small_d = small.to(device, non_blocking=True)
-            params = small_d[:B * 4].view(torch.float32).view(B, 8)
-            poff_d = small_d[o:o + B + 1]
-            ioff_d = small_d[o + B + 1:o + 2 * B + 2]
-            seeds = small_d[o + 2 * B + 2:o + 3 * B + 2]
-            shapes = small_d[o + 3 * B + 2:o + 3 * B + 2 + 2 * B].view(torch.int32).view(B, 4)
+            sd = {k: small_d[a:b].view(getattr(torch, str(words[k].dtype))) for k, (a, b) in at.items()}
+            sd["shapes"] = sd["shapes"].view(B, 4)
+            raw_d, poff_d = self.source_records(big_d, sd, img_d)
             floor = ops.points_floor(raw_d, poff_d)
-            points = ops.points_prep(raw_d, poff_d, floor, params, seeds, self.num_points)
-            img = ops.image_prep(img_d, ioff_d, shapes, (Hp, Wp), *self.img_norm)
+            points = ops.points_prep(raw_d, poff_d, floor, sd["params"].view(B, 8), sd["seeds"], self.num_points)
+            img = ops.image_prep(img_d, sd["ioff"], sd["shapes"], (Hp, Wp), *self.img_norm)
             batch = dict(points=points, img=img, img_metas=metas)
             if all(s["gt_labels_3d"] is not None for s in scenes):
                 batch["gt_bboxes_3d"] = [torch.from_numpy(np.ascontiguousarray(s["gt_bboxes_3d"])).to(device)
                                          for s in scenes]
                 batch["gt_labels_3d"] = [torch.from_numpy(np.ascontiguousarray(s["gt_labels_3d"])).to(device)
                                          for s in scenes]
-        uploaded = raw_h.numel() * 4 + img_h.numel() + small.numel() * 8
+        uploaded = sum(t.numel() * t.element_size() for t in big.values()) + img_h.numel() + small.numel() * 8
         return batch, uploaded
+
+
+class FramePipeline(ScenePipeline):
+    """``ScenePipeline`` in test mode over raw RGB-D frames (``dataset.RGBDFrames``): the host decodes the colour
+    image and the 16-bit depth PNG; the depth words are uploaded as they are and ``ops.depth_to_points`` makes the
+    records on the device from them and from the colour bytes that ``image_prep`` reads anyway.  The valid-pixel
+    counts stay on the device.  Everything else - metadata, point sample, image - is ``ScenePipeline``'s."""
+
+    def __init__(self, dataset, img_scale=(1333, 800), num_points=20000, seed=0, img_norm=ops.IMG_NORM,
+                 pad_divisor=32):
+        super().__init__(dataset, "test", img_scale, num_points, seed, img_norm, pad_divisor)
+
+    @staticmethod
+    def read_depth(path):
+        """A 16-bit depth PNG -> (h, w) uint16, the stored words untouched."""
+        from PIL import Image
+        with Image.open(path) as im:
+            if im.mode not in ("I;16", "I;16L", "I;16B", "I;16N"):
+                raise ValueError(f"{path}: depth must be a 16-bit greyscale image (PIL mode 'I;16'), got mode "
+                                 f"{im.mode!r}")
+            d = np.asarray(im)
+        if d.dtype != np.uint16 or d.ndim != 2:
+            raise ValueError(f"{path}: depth decoded as {d.dtype} {d.shape}, expected a 2-D uint16 image")
+        return np.ascontiguousarray(d)
+
+    def load(self, index, epoch=0):
+        """Host part of one frame: colour and depth decode, metadata, the point sample's seed."""
+        info = self.dataset.get_data_info(index)
+        img = self.read_image(info["img_filename"])
+        depth = self.read_depth(info["depth_filename"])
+        if depth.shape != img.shape[:2]:
+            raise ValueError(f"{info['depth_filename']}: depth is {depth.shape}, the image {img.shape[:2]}; colour "
+                             "and depth must be registered")
+        return self._scene(index, epoch, info, img, dict(depth_filename=info["depth_filename"]), depth=depth,
+                           calib=self.dataset.calib_row(info["calib"]))
+
+    def pack_source(self, scenes):
+        npix = np.array([s["depth"].size for s in scenes], np.int64)
+        depth_h = torch.empty((int(npix.sum()),), dtype=torch.uint16, pin_memory=True)
+        depth_np = depth_h.numpy()
+        doff = np.concatenate([[0], np.cumsum(npix)]).astype(np.int64)
+        for b, s in enumerate(scenes):
+            depth_np[doff[b]:doff[b + 1]] = s["depth"].reshape(-1)
+        return dict(depth=depth_h), dict(doff=doff, calib=np.stack([s["calib"] for s in scenes]).astype(np.float64))
+
+    def source_records(self, big, small, img_d):
+        B = small["doff"].numel() - 1
+        return ops.depth_to_points(big["depth"], small["doff"], img_d, small["ioff"], small["shapes"],
+                                   small["calib"].view(B, 16), self.dataset.shift)
 
 
 class SceneBatch(dict):
@@ -217,11 +294,19 @@ class SceneLoader:
 
     Train mode reshuffles per epoch (a permutation keyed on (seed, epoch)) and draws every scene's augmentation from
     (seed, epoch, index); iterating the loader again runs the next epoch (RepeatDataset(times=5) is five epochs).
-    Test mode keeps the dataset order, with no augmentation; the point sample is keyed on (seed, index)."""
+    Test mode keeps the dataset order, with no augmentation; the point sample is keyed on (seed, index).
 
-    def __init__(self, dataset, batch_size, mode="train", seed=0, img_scale=(1333, 800), num_points=20000,
-                 workers=8, drop_last=False, device=None):
-        self.pipeline = ScenePipeline(dataset, mode, img_scale, num_points, seed)
+    ``pipeline``: an instance (e.g. ``FramePipeline`` over ``RGBDFrames``) to use in place of the ``ScenePipeline``
+    the loader would build; it then brings its own ``img_scale`` / ``num_points`` / ``seed``, and ``mode`` defaults
+    to its mode (``"train"`` otherwise)."""
+
+    def __init__(self, dataset, batch_size, mode=None, seed=0, img_scale=(1333, 800), num_points=20000,
+                 workers=8, drop_last=False, device=None, pipeline=None):
+        if mode is None:
+            mode = "train" if pipeline is None else pipeline.mode
+        if pipeline is not None and pipeline.mode != mode:
+            raise ValueError(f"the given pipeline is in {pipeline.mode!r} mode, the loader in {mode!r}")
+        self.pipeline = ScenePipeline(dataset, mode, img_scale, num_points, seed) if pipeline is None else pipeline
         self.dataset, self.batch_size, self.mode, self.seed = dataset, int(batch_size), mode, int(seed)
         self.drop_last = drop_last
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)

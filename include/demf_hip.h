@@ -896,6 +896,27 @@ DEMF_INTERNAL int demf_image_prep(int B, int Hp, int Wp, long long src_bytes, co
                     demf_stream_t stream);
 
 /* ------------------------------------------------------------------ *
+ * RGB-D frame front end (csrc/frame.hip): what the SUN RGB-D toolbox's offline export does per pixel (unproject the
+ * depth image, apply the tilt matrix) [dep-recall], so that a raw frame can take the place of a scene's `.bin`.
+ * B ragged frames: depth = their row-major uint16 images concatenated (`total` pixels, depth_off (B+1) int64 pixel
+ * offsets), rgb / rgb_off / shapes = the buffers of demf_image_prep (shapes (B,4) int32, the first two read as h, w),
+ * calib (B,16) fp64 = [fx, fy, cx, cy, Rt row-major (9), pixel_origin, depth_scale, z_max]; all DEVICE arrays.
+ * Pixel (row v, column u), fp64, one IEEE operation at a time (no contraction):
+ *   d' = d rotated right by `shift` in 16 bits; the pixel is valid iff d' != 0
+ *   z  = min(d' / depth_scale, z_max);  x3 = ((u + pixel_origin) - cx) * z / fx;  y3 = ((v + pixel_origin) - cy) * z / fy
+ *   c  = (x3, z, -y3);  p_i = (Rt[i][0] c0 + Rt[i][1] c1) + Rt[i][2] c2
+ *   record = fp32(p_0), fp32(p_1), fp32(p_2), fp32(r) / 255, fp32(g) / 255, fp32(b) / 255
+ * raw (total, 6) fp32 receives the records of the valid pixels only, frames in order and row-major inside a frame;
+ * rows at or beyond offsets[B] are not written.  offsets (B+1) int64 (DEVICE): offsets[b+1] - offsets[b] = frame b's
+ * valid pixels - the (raw, offsets) pair of demf_points_floor / demf_points_prep.  A frame whose table entries do
+ * not lie inside the buffers has no valid pixel.  tile_counts: ntiles = ceil(total / 1024) ints of scratch.  Two
+ * launches, no atomics: the result is bit-identical from run to run.                                              */
+DEMF_INTERNAL int demf_depth_to_points(int B, long long total, long long rgb_bytes, int shift,
+                         const unsigned short* depth, const int64_t* depth_off, const unsigned char* rgb,
+                         const int64_t* rgb_off, const int* shapes, const double* calib, int ntiles,
+                         int* tile_counts, float* raw, int64_t* offsets, demf_stream_t stream);
+
+/* ------------------------------------------------------------------ *
  * Optimizer step on flat buffers: torch.optim.AdamW + clip_grad_norm_ as the reference's
  * runner applies them (configs/_base_/schedules/schedule_3x.py:6-7: AdamW lr 0.008, wd 0.01,
  * grad_clip max_norm 10; configs/demf/demf_votenet.py:16-24: 'decoder' lr_mult 0.05).  One call
