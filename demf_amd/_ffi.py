@@ -55,6 +55,7 @@ SIGNATURES = {
     "demf_box_extent_count": [_c_int] * 4 + [_ptr] * 8,
     "demf_aligned_nms": [_c_int, _c_int, _c_float] + [_ptr] * 6,
     "demf_detect_decode": [_c_int] * 6 + [_ptr] * 7 + [_ptr],
+    "demf_ca_detect_decode": [_c_int] * 5 + [_ptr, _c_int, _c_int] * 3 + [_ptr] * 6 + [_ptr],
     "demf_detect_pack": [_c_int] * 4 + [_c_float] + [_ptr] * 5 + [_c_int] * 3 + [_ptr] * 5 + [_ptr],
     "demf_box3d_iou": [_c_int, _c_int] + [_ptr] * 4,
     "demf_eval_match": [_c_int, _c_int, _ptr, _c_int, _c_int] + [_ptr] * 7,
@@ -130,6 +131,8 @@ SIGNATURES = {
     "demf_mlp_gemm_bwd_dw_ld": [_c_int] * 4 + [_ptr] * 3 + [_c_int] + [_ptr] * 5 + [_c_int, _ptr],
     "demf_head_loss_fwd": [_c_int] * 3 + [_ptr] * 14,
     "demf_head_loss_bwd": [_c_int] * 3 + [_ptr] * 17,
+    "demf_ca_head_loss_fwd": [_c_int] * 3 + [_ptr] * 12,
+    "demf_ca_head_loss_bwd": [_c_int] * 3 + [_ptr] * 16,
     "demf_vote_loss": [_c_int] * 4 + [_c_float] + [_ptr] * 10,
     "demf_vote_loss_fwd": [_c_int] * 4 + [_c_float] + [_ptr] * 8,
     "demf_msda_fwd_f32": [_c_int] * 7 + [_ptr] * 7,

@@ -18,6 +18,48 @@ __device__ __forceinline__ const float* row_of(const float* p, int sb, int sk, i
   return p + (size_t)b * sb + (size_t)k * sk;
 }
 
+// Scores of one candidate: obj = softmax(obj_scores)[1]; sem = softmax(sem_scores); cls = argmax(sem) (first maximum).
+__device__ __forceinline__ void score_one(const float* ob, const float* sm, size_t g, int C, float* __restrict__ obj,
+                                          float* __restrict__ sem, long long* __restrict__ cls) {
+  // F.softmax: exp(x - max) / sum
+  {
+    const float mx = fmaxf(ob[0], ob[1]);
+    const float e0 = expf(ob[0] - mx), e1 = expf(ob[1] - mx);
+    obj[g] = e1 / (e0 + e1);
+  }
+  float mx = sm[0];
+  for (int j = 1; j < C; ++j) mx = fmaxf(mx, sm[j]);
+  float sum = 0.f;
+  for (int j = 0; j < C; ++j) sum += expf(sm[j] - mx);
+  float* so = sem + g * C;
+  int best = 0;
+  float bp = -1.f;
+  for (int j = 0; j < C; ++j) {
+    const float p = expf(sm[j] - mx) / sum;
+    so[j] = p;
+    if (p > bp) { bp = p; best = j; }
+  }
+  cls[g] = best;
+}
+
+// yaw = class2angle(argmax dir_class, res_scale * dir_res[argmax]) % 2pi, in torch's fp32 steps
+__device__ __forceinline__ float yaw_of(const float* dc, const float* dr, float res_scale, int nb) {
+  int best = 0;
+  float bv = dc[0];
+  for (int j = 1; j < nb; ++j) {
+    const float v = dc[j];
+    if (v > bv) { bv = v; best = j; }
+  }
+  const float res = dr[best] * res_scale;
+  const float two_pi = (float)(2.0 * 3.14159265358979323846);
+  const float per = (float)(2.0 * 3.14159265358979323846 / (double)nb);
+  float angle = (float)best * per + res;                                   // class2angle
+  if (angle > (float)3.14159265358979323846) angle = angle - two_pi;       // limit_period
+  float m = fmodf(angle, two_pi);                                          // torch.remainder(angle, 2pi)
+  if (m != 0.f && m < 0.f) m += two_pi;
+  return m;
+}
+
 // One candidate: box7 = coder.decode(): (centre, size, yaw) with yaw = class2angle(argmax dir_class,
 // dir_res[argmax]) % 2pi; obj = softmax(obj_scores)[1]; sem = softmax(sem_scores); cls = argmax(sem) (first maximum).
 __device__ __forceinline__ void decode_one(const demf_detect_layer& y, int b, int k, size_t g, int C, int nb,
@@ -36,47 +78,14 @@ __device__ __forceinline__ void decode_one(const demf_detect_layer& y, int b, in
   for (int a = 0; a < 3; ++a) o[3 + a] = sz[a];
   float yaw = 0.f;
   if (with_rot) {
-    const float* dc = row_of(y.dir_class, y.dir_class_sb, y.dir_class_sk, b, k);
-    int best = 0;
-    float bv = dc[0];
-    for (int j = 1; j < nb; ++j) {
-      const float v = dc[j];
-      if (v > bv) { bv = v; best = j; }
-    }
     // coder.py:233  dir_res = dir_res_norm * (pi / nb)  (res_scale = 1 when dir_res itself is given)
-    const float res = row_of(y.dir_res, y.dir_res_sb, y.dir_res_sk, b, k)[best] * y.res_scale;
-    const float two_pi = (float)(2.0 * 3.14159265358979323846);
-    const float per = (float)(2.0 * 3.14159265358979323846 / (double)nb);
-    float angle = (float)best * per + res;                                   // class2angle
-    if (angle > (float)3.14159265358979323846) angle = angle - two_pi;       // limit_period
-    float m = fmodf(angle, two_pi);                                          // torch.remainder(angle, 2pi)
-    if (m != 0.f && m < 0.f) m += two_pi;
-    yaw = m;
+    yaw = yaw_of(row_of(y.dir_class, y.dir_class_sb, y.dir_class_sk, b, k),
+                 row_of(y.dir_res, y.dir_res_sb, y.dir_res_sk, b, k), y.res_scale, nb);
   }
   o[6] = yaw;
   cosy[g] = cosf(yaw);
   siny[g] = sinf(yaw);
-  // F.softmax: exp(x - max) / sum
-  const float* ob = row_of(y.obj, y.obj_sb, y.obj_sk, b, k);
-  {
-    const float mx = fmaxf(ob[0], ob[1]);
-    const float e0 = expf(ob[0] - mx), e1 = expf(ob[1] - mx);
-    obj[g] = e1 / (e0 + e1);
-  }
-  const float* sm = row_of(y.sem, y.sem_sb, y.sem_sk, b, k);
-  float mx = sm[0];
-  for (int j = 1; j < C; ++j) mx = fmaxf(mx, sm[j]);
-  float sum = 0.f;
-  for (int j = 0; j < C; ++j) sum += expf(sm[j] - mx);
-  float* so = sem + g * C;
-  int best = 0;
-  float bp = -1.f;
-  for (int j = 0; j < C; ++j) {
-    const float p = expf(sm[j] - mx) / sum;
-    so[j] = p;
-    if (p > bp) { bp = p; best = j; }
-  }
-  cls[g] = best;
+  score_one(row_of(y.obj, y.obj_sb, y.obj_sk, b, k), row_of(y.sem, y.sem_sb, y.sem_sk, b, k), g, C, obj, sem, cls);
 }
 
 // One lane per candidate (scene b, proposal kk of the concatenated K = sum K_l).  The layer loop index is uniform, so
@@ -99,6 +108,41 @@ __global__ __launch_bounds__(256) void detect_decode_k(int B, int K, int L, int 
       lo += Kl;
     }
   }
+}
+
+// The distance form (CAVoteHead: ClassAgnosticBBoxCoder.decode, class_agnostic_bbox_coder.py:42-86): one lane per
+// proposal, straight from the raw conv rows.  d = exp(reg[0:6]) (split_pred, :100); size = clamp(d[0:3] + d[3:6],
+// min=0.1) (:67-68); canonical = (d[3:6] - d[0:3]) / 2 (:71-72) rotated by yaw about z as mmdet3d's
+// rotation_3d_in_axis does (x c + y s, -x s + y c, z); centre = ref - that (:83).
+__global__ __launch_bounds__(256) void ca_detect_decode_k(int B, int K, int C, int nb, int with_rot,
+                                                          const float* __restrict__ reg, int reg_sb, int reg_sk,
+                                                          const float* __restrict__ cls_rows, int cls_sb, int cls_sk,
+                                                          const float* __restrict__ ref, int ref_sb, int ref_sk,
+                                                          float* __restrict__ box7, float* __restrict__ cosy,
+                                                          float* __restrict__ siny, float* __restrict__ obj,
+                                                          float* __restrict__ sem, long long* __restrict__ cls) {
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= B * K) return;
+  const int b = g / K, k = g - b * K;
+  const float* pr = row_of(reg, reg_sb, reg_sk, b, k);
+  const float* pc = row_of(cls_rows, cls_sb, cls_sk, b, k);
+  const float* rp = row_of(ref, ref_sb, ref_sk, b, k);
+  float d[6];
+#pragma unroll
+  for (int a = 0; a < 6; ++a) d[a] = expf(pr[a]);
+  const float yaw = with_rot ? yaw_of(pr + 6, pr + 6 + nb, (float)(3.14159265358979323846 / (double)nb), nb) : 0.f;
+  const float c = cosf(yaw), s = sinf(yaw);
+  const float x = (d[3] - d[0]) / 2.f, y = (d[4] - d[1]) / 2.f, z = (d[5] - d[2]) / 2.f;
+  float* o = box7 + (size_t)g * 7;
+  o[0] = rp[0] - (x * c + y * s);
+  o[1] = rp[1] - ((-x) * s + y * c);
+  o[2] = rp[2] - z;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) o[3 + a] = fmaxf(d[a] + d[3 + a], 0.1f);
+  o[6] = yaw;
+  cosy[g] = c;
+  siny[g] = s;
+  score_one(pc, pc + 2, (size_t)g, C, obj, sem, cls);
 }
 
 // Block-wide sum of one int per thread (1024 threads = 16 waves); every thread receives the total.
@@ -205,6 +249,27 @@ extern "C" int demf_detect_decode(int B, int K, int L, int C, int num_dir_bins, 
   hipLaunchKernelGGL(detect_decode_k, dim3(cdiv(B * K, 256)), dim3(256), 0, (hipStream_t)stream, B, K, L, C,
                      num_dir_bins, with_rot, arg, box7, cos_yaw, sin_yaw, obj, sem, (long long*)classes);
   return check_launch("detect_decode");
+}
+
+extern "C" int demf_ca_detect_decode(int B, int K, int C, int num_dir_bins, int with_rot, const float* reg,
+                                     int reg_sb, int reg_sk, const float* cls, int cls_sb, int cls_sk,
+                                     const float* ref, int ref_sb, int ref_sk, float* box7, float* cos_yaw,
+                                     float* sin_yaw, float* obj, float* sem, int64_t* classes,
+                                     demf_stream_t stream) {
+  DEMF_REQUIRE(B >= 0 && K >= 0 && C >= 1 && num_dir_bins >= 1, "ca_detect_decode: bad sizes");
+  if (K > 1024) {
+    set_error("ca_detect_decode: K=%d boxes per scene exceeds 1024", K);
+    return DEMF_EUNSUPPORTED;
+  }
+  if (B * K == 0) return DEMF_OK;
+  DEMF_REQUIRE(reg_sk >= 6 + 2 * num_dir_bins && cls_sk >= 2 + C && ref_sk >= 3 && reg_sb >= 0 && cls_sb >= 0 &&
+                   ref_sb >= 0, "ca_detect_decode: bad strides");
+  DEMF_REQUIRE(reg && cls && ref && box7 && cos_yaw && sin_yaw && obj && sem && classes,
+               "ca_detect_decode: null pointer");
+  hipLaunchKernelGGL(ca_detect_decode_k, dim3(cdiv(B * K, 256)), dim3(256), 0, (hipStream_t)stream, B, K, C,
+                     num_dir_bins, with_rot, reg, reg_sb, reg_sk, cls, cls_sb, cls_sk, ref, ref_sb, ref_sk, box7,
+                     cos_yaw, sin_yaw, obj, sem, (long long*)classes);
+  return check_launch("ca_detect_decode");
 }
 
 extern "C" int demf_detect_pack(int B, int K, int C, int per_class, float score_thr,

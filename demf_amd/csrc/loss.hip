@@ -197,6 +197,211 @@ __global__ __launch_bounds__(256) void head_loss_bwd_k(
   for (int k = 0; k < 3; ++k) gbase[r * 3 + k] = gr[k];   // centre = base + offset
 }
 
+// ---- distance form: CAVoteHead.loss (class_agnostic_vote_head.py:40-121) -----------------------
+// The points-only baseline's head regresses the log of the six distances from the proposal to the box
+// faces: reg row (30) = [log-distance 6 | dir class 12 | dir residual 12], distance = exp(reg[0:6])
+// (ClassAgnosticBBoxCoder.split_pred, class_agnostic_bbox_coder.py:88-127).  Its IoU loss compares the corners
+// (ref - d[3:6], ref + d[0:3]) with the same built from the targets: both boxes hang on the SAME reference
+// point, so every quantity of the IoU is a function of the distances alone - extent_k = min(d_k, t_k) +
+// min(d_3+k, t_3+k) (never negative: d > 0, t >= 0), side_k = d_k + d_3+k - and the point is not read.  (The point
+// does get a gradient in the reference, through the distance TARGETS: see the end of the backward kernel.)
+// Both kernels read the whole cls / reg row into registers before anything is computed from it: the residual
+// at the target direction class is then a register select, not a second load that waits for the first.
+constexpr int CA_NLOSS = 6;                                  // the seven slots without the centre one
+__device__ __forceinline__ int ca_slot(int i) { return i < 4 ? i : i + 1; }   // 0 1 2 3 5 6
+
+// One row into registers: cls (12), the direction class logits dc (12) and residuals dr (12) of reg, the clamped
+// distance targets t (6) and d = exp(reg[0:6]).
+__device__ __forceinline__ void ca_load(int r, const float* __restrict__ cls, const float* __restrict__ reg,
+                                        const float* __restrict__ dist_t, float* wc, float* dc, float* dr,
+                                        float* d, float* t) {
+  const float* pc = cls + (size_t)r * 12;
+  const float* pr = reg + (size_t)r * 30;
+  const float* pt = dist_t + (size_t)r * 6;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) wc[i] = pc[i];
+  float lg[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) lg[i] = pr[i];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) dc[i] = pr[6 + i];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) dr[i] = pr[18 + i];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) t[i] = fmaxf(pt[i], 0.f);      // distance_targets.clamp_(min=0), :301
+#pragma unroll
+  for (int i = 0; i < 6; ++i) d[i] = expf(lg[i]);
+}
+
+// ce<> above on a register array: every index is a compile-time constant after unrolling (the target is
+// picked by selects), so the row never goes to scratch memory; the arithmetic is the same, term by term
+template <int N>
+__device__ __forceinline__ float ce_reg(const float* p, int t, float* grad /*nullable*/, float gscale) {
+  float m = p[0];
+#pragma unroll
+  for (int i = 1; i < N; ++i) m = fmaxf(m, p[i]);
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < N; ++i) s += __expf(p[i] - m);
+  const float lse = m + __logf(s);
+  float pt = p[0];
+#pragma unroll
+  for (int i = 1; i < N; ++i) pt = i == t ? p[i] : pt;
+  if (grad) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) grad[i] += gscale * (__expf(p[i] - lse) - (i == t ? 1.f : 0.f));
+  }
+  return lse - pt;
+}
+
+// v[j] of a 12-element register array, j in 0..11
+__device__ __forceinline__ float pick12(const float* v, int j) {
+  float r = v[0];
+#pragma unroll
+  for (int i = 1; i < 12; ++i) r = i == j ? v[i] : r;
+  return r;
+}
+
+struct CaIoU {
+  float iou, overlap, uni;
+  float ext[3], side[3];       // intersection extent, predicted box side, per axis
+  bool clamped;
+};
+
+__device__ __forceinline__ CaIoU ca_iou(const float* d, const float* t) {
+  CaIoU r;
+  float a1 = 1.f, a2 = 1.f, ov = 1.f;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    r.side[k] = d[k] + d[3 + k];
+    r.ext[k] = fminf(d[k], t[k]) + fminf(d[3 + k], t[3 + k]);
+    a1 *= r.side[k];
+    a2 *= (t[k] + t[3 + k]);
+    ov *= r.ext[k];
+  }
+  r.overlap = ov;
+  const float u = a1 + a2 - ov;
+  r.clamped = u < 1e-6f;
+  r.uni = r.clamped ? 1e-6f : u;
+  r.iou = ov / r.uni;
+  return r;
+}
+
+__global__ __launch_bounds__(256) void ca_head_loss_fwd_k(
+    HeadLossCfg c, const float* __restrict__ cls, const float* __restrict__ reg,
+    const float* __restrict__ dist_t, const long long* __restrict__ dircls_t,
+    const float* __restrict__ dirres_t, const long long* __restrict__ sem_t,
+    const long long* __restrict__ obj_t, const float* __restrict__ obj_w,
+    const float* __restrict__ box_w, float* __restrict__ out) {
+  __shared__ float red[CA_NLOSS][256];
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  float l[CA_NLOSS] = {0, 0, 0, 0, 0, 0};   // objectness, dir_class, dir_res, size_res (distances), semantic, iou
+  if (r < c.R) {
+    float wc[12], dc[12], dr[12], d[6], t[6];
+    ca_load(r, cls, reg, dist_t, wc, dc, dr, d, t);
+    const float ow = obj_w[r], rt = dirres_t[r], bw = box_w[r];
+    const int ot = (int)obj_t[r], dt = (int)dircls_t[r], st = (int)sem_t[r];
+    l[0] = c.w_obj * ow * (ot ? c.cw1 : c.cw0) * ce_reg<2>(wc, ot, nullptr, 0.f);
+    if (bw != 0.f) {   // every box term carries the weight objectness_target / n_pos
+      l[1] = c.w_dircls * bw * ce_reg<12>(dc, dt, nullptr, 0.f);
+      l[2] = c.w_dirres * bw * smooth_l1(pick12(dr, dt) - rt, c.beta_dirres);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) l[3] += c.w_size * bw * smooth_l1(d[k] - t[k], c.beta_size);
+      l[4] = c.w_sem * bw * ce_reg<10>(wc + 2, st, nullptr, 0.f);
+      l[5] = c.w_iou * bw * (1.f - ca_iou(d, t).iou);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < CA_NLOSS; ++i) red[i][threadIdx.x] = l[i];
+  __syncthreads();
+  for (int sft = 128; sft > 0; sft >>= 1) {
+    if (threadIdx.x < sft)
+#pragma unroll
+      for (int i = 0; i < CA_NLOSS; ++i) red[i][threadIdx.x] += red[i][threadIdx.x + sft];
+    __syncthreads();
+  }
+  if (threadIdx.x < CA_NLOSS) atomicAdd(out + ca_slot(threadIdx.x), red[threadIdx.x][0]);
+}
+
+// gradients wrt cls (R,12) and reg (R,30); d distance / d reg = distance
+__global__ __launch_bounds__(256) void ca_head_loss_bwd_k(
+    HeadLossCfg c, const float* __restrict__ cls, const float* __restrict__ reg,
+    const float* __restrict__ dist_t, const long long* __restrict__ dircls_t,
+    const float* __restrict__ dirres_t, const long long* __restrict__ sem_t,
+    const long long* __restrict__ obj_t, const float* __restrict__ obj_w,
+    const float* __restrict__ box_w, const float* __restrict__ gout,
+    const float* __restrict__ yaw_t /*nullable: boxes without rotation*/,
+    float* __restrict__ gcls, float* __restrict__ greg, float* __restrict__ gref /*nullable*/) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= c.R) return;
+  float wc[12], dc[12], dr[12], d[6], t[6];
+  ca_load(r, cls, reg, dist_t, wc, dc, dr, d, t);
+  float gt[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // d total / d (clamped) distance target
+  const float ow = obj_w[r], rt = dirres_t[r], bw = box_w[r];
+  const int ot = (int)obj_t[r], dt = (int)dircls_t[r], st = (int)sem_t[r];
+  float gc[12], gr[30];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) gc[i] = 0.f;
+#pragma unroll
+  for (int i = 0; i < 30; ++i) gr[i] = 0.f;
+  ce_reg<2>(wc, ot, gc, gout[0] * c.w_obj * ow * (ot ? c.cw1 : c.cw0));
+  if (bw != 0.f) {
+    ce_reg<12>(dc, dt, gr + 6, gout[1] * c.w_dircls * bw);
+    const float g_res = gout[2] * c.w_dirres * bw *
+                        smooth_l1_grad(pick12(dr, dt) - rt, c.beta_dirres);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) gr[18 + i] = i == dt ? g_res : 0.f;
+    ce_reg<10>(wc + 2, st, gc + 2, gout[5] * c.w_sem * bw);
+    // IoU: loss = 1 - ov / u;  d iou = (d ov * u - ov * d u) / u^2, d u = d a1 - d ov (clamped union: d u = 0)
+    const CaIoU u = ca_iou(d, t);
+    const float gl = -gout[6] * c.w_iou * bw;          // d total / d iou
+    const float inv_u = 1.f / u.uni;
+    const float k_ov = gl * (inv_u + (u.clamped ? 0.f : u.overlap * inv_u * inv_u));
+    const float k_a1 = u.clamped ? 0.f : -gl * u.overlap * inv_u * inv_u;
+    const float g_sl1 = gout[3] * c.w_size * bw;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float other_ov = u.ext[(k + 1) % 3] * u.ext[(k + 2) % 3];
+      const float other_a1 = u.side[(k + 1) % 3] * u.side[(k + 2) % 3];
+      const float other_a2 = (t[(k + 1) % 3] + t[(k + 1) % 3 + 3]) * (t[(k + 2) % 3] + t[(k + 2) % 3 + 3]);
+#pragma unroll
+      for (int f = k; f < 6; f += 3) {
+        // torch.min / torch.max backward: a tie splits the gradient evenly between both operands
+        const float wmin = d[f] < t[f] ? 1.f : (d[f] == t[f] ? 0.5f : 0.f);
+        const float sl1 = g_sl1 * smooth_l1_grad(d[f] - t[f], c.beta_size);
+        const float g_d = sl1 + (k_ov * other_ov * wmin + k_a1 * other_a1);
+        gr[f] = g_d * d[f];
+        // the target's side of the same terms: the union holds a1 and a2 alike (k_a1 serves both)
+        gt[f] = -sl1 + (k_ov * other_ov * (1.f - wmin) + k_a1 * other_a2);
+      }
+    }
+  }
+  if (gref) {
+    // The reference builds the distance targets from the proposal point WITH its gradient attached
+    // (class_agnostic_vote_head.py:271-294: t = dims / 2 -+ Rz(-yaw) (point - centre), then clamp_(min=0), :301), so
+    // the loss reaches the aggregated points through its TARGETS: d t[0:3] / d local = -1, d t[3:6] / d local = +1
+    // where the raw target is >= 0 (clamp's backward passes the gradient AT 0), local = (x c + y s, -x s + y c, z)
+    // with c, s = cos, sin(-yaw) as proposal_targets_k applies them.
+    const float* raw = dist_t + (size_t)r * 6;
+    float gl3[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      gl3[k] = (raw[3 + k] >= 0.f ? gt[3 + k] : 0.f) - (raw[k] >= 0.f ? gt[k] : 0.f);
+    float cs = 1.f, sn = 0.f;
+    if (yaw_t) {
+      cs = cosf(-yaw_t[r]);
+      sn = sinf(-yaw_t[r]);
+    }
+    gref[(size_t)r * 3] = gl3[0] * cs - gl3[1] * sn;
+    gref[(size_t)r * 3 + 1] = gl3[0] * sn + gl3[1] * cs;
+    gref[(size_t)r * 3 + 2] = gl3[2];
+  }
+#pragma unroll
+  for (int i = 0; i < 12; ++i) gcls[(size_t)r * 12 + i] = gc[i];
+#pragma unroll
+  for (int i = 0; i < 30; ++i) greg[(size_t)r * 30 + i] = gr[i];
+}
+
 // ---- vote loss: sum over seeds of min_j L1(vote - (gt_vote_j + seed)) * mask/(sum mask) * w --
 // COUNT (forward only): the number of seeds on a positive point - the denominator, torch.gather(mask, 1,
 // seed_indices).sum() in the reference's VoteModule.get_loss - is counted here by every workgroup
@@ -737,4 +942,39 @@ extern "C" int demf_loss_total_bwd(int n, const float* g8, float* gvecs, float* 
   DEMF_REQUIRE(n >= 1 && n <= 4 && g8 && gvecs, "loss_total_bwd: 1..4 seven-vectors");
   hipLaunchKernelGGL(loss_total_bwd_k, dim3(1), dim3(64), 0, (hipStream_t)stream, n, g8, gvecs, gvote);
   return check_launch("loss_total_bwd");
+}
+
+extern "C" int demf_ca_head_loss_fwd(int R, int num_dir_bins, int num_classes, const float* hyper12,
+                                     const float* cls, const float* reg, const float* distance_t,
+                                     const int64_t* dir_class_t, const float* dir_res_t,
+                                     const int64_t* sem_t, const int64_t* obj_t, const float* obj_w,
+                                     const float* box_w, float* out7, demf_stream_t stream) {
+  DEMF_REQUIRE(R >= 0 && num_dir_bins == 12 && num_classes == 10,
+               "ca_head_loss: only the reference layout (12 direction bins, 10 classes) is built");
+  if (R == 0) return DEMF_OK;
+  DEMF_REQUIRE(hyper12 && cls && reg && distance_t && dir_class_t && dir_res_t && sem_t && obj_t && obj_w &&
+                   box_w && out7, "ca_head_loss_fwd: null pointer");
+  hipLaunchKernelGGL(ca_head_loss_fwd_k, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream,
+                     make_cfg(R, hyper12), cls, reg, distance_t, (const long long*)dir_class_t, dir_res_t,
+                     (const long long*)sem_t, (const long long*)obj_t, obj_w, box_w, out7);
+  return check_launch("ca_head_loss_fwd");
+}
+
+extern "C" int demf_ca_head_loss_bwd(int R, int num_dir_bins, int num_classes, const float* hyper12,
+                                     const float* cls, const float* reg, const float* distance_t,
+                                     const int64_t* dir_class_t, const float* dir_res_t,
+                                     const int64_t* sem_t, const int64_t* obj_t, const float* obj_w,
+                                     const float* box_w, const float* grad_out7, const float* dir_t,
+                                     float* grad_cls, float* grad_reg, float* grad_ref,
+                                     demf_stream_t stream) {
+  DEMF_REQUIRE(R >= 0 && num_dir_bins == 12 && num_classes == 10,
+               "ca_head_loss: only the reference layout (12 direction bins, 10 classes) is built");
+  if (R == 0) return DEMF_OK;
+  DEMF_REQUIRE(hyper12 && cls && reg && distance_t && dir_class_t && dir_res_t && sem_t && obj_t && obj_w &&
+                   box_w && grad_out7 && grad_cls && grad_reg, "ca_head_loss_bwd: null pointer");
+  hipLaunchKernelGGL(ca_head_loss_bwd_k, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream,
+                     make_cfg(R, hyper12), cls, reg, distance_t, (const long long*)dir_class_t, dir_res_t,
+                     (const long long*)sem_t, (const long long*)obj_t, obj_w, box_w, grad_out7, dir_t, grad_cls,
+                     grad_reg, grad_ref);
+  return check_launch("ca_head_loss_bwd");
 }

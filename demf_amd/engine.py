@@ -510,8 +510,12 @@ class Trainer:
         # (the fused decoder layer advances its counter-based dropout state by itself, inside the
         # forward and therefore inside the captured graph: demf_amd/fused.py)
         fwd = self.model.forward_train if self._forward is None else self._forward
-        losses = fwd(batch["points"], batch["img_features"], batch["img_metas"], batch["gt_bboxes_3d"],
-                     batch["gt_labels_3d"], **kw)
+        if "img_features" in batch:
+            losses = fwd(batch["points"], batch["img_features"], batch["img_metas"], batch["gt_bboxes_3d"],
+                         batch["gt_labels_3d"], **kw)
+        else:
+            # a points-only batch (modules.VoteNet: no image stream, nothing to stage or refresh per batch)
+            losses = fwd(batch["points"], batch.get("img_metas"), batch["gt_bboxes_3d"], batch["gt_labels_3d"], **kw)
         if self.meter is not None:
             missing = [k for k in self.meter.names if k not in losses]
             if missing:
@@ -806,21 +810,24 @@ class Trainer:
             gt, lab = self.pad_targets(batch["gt_bboxes_3d"], batch["gt_labels_3d"], G, dev)
         else:
             G, gt, lab = None, batch["gt_bboxes_3d"], batch["gt_labels_3d"]
-        feats = batch["img_features"]
-        head = getattr(self.model, "pts_bbox_head", None)
+        feats = batch.get("img_features")            # None: a points-only batch - every image block below is skipped
+        head = getattr(self.model, "pts_bbox_head", None) if feats is not None else None
         # A pyramid handed over as the reference's list of (B,C,H_l,W_l) maps: the captured step reads TOKENS
         # (channels-last rows, padding zeroed) from a static buffer, and ``load`` converts every new batch
         # straight out of the caller's maps into that buffer (one tiled-transpose launch) - instead of copying
         # the 152 MB pyramid into static maps and transposing those inside the graph.
         tok_static = None
-        if (not isinstance(feats, dict) and dev.type == "cuda" and hasattr(head, "pyramid_tokens")
+        if (feats is not None and not isinstance(feats, dict) and dev.type == "cuda" and hasattr(head, "pyramid_tokens")
                 and switches.env_int("DEMF_ZERO_COPY_TOKENS")):
             tok_static = head.pyramid_tokens(feats, batch["img_metas"])
-        static = dict(points=batch["points"].clone(),
-                      img_features=(tok_static if tok_static is not None else
-                                    dict(feats, tokens=feats["tokens"].clone())
-                                    if isinstance(feats, dict) else [f.clone() for f in feats]),
-                      img_metas=batch["img_metas"], gt_bboxes_3d=gt, gt_labels_3d=lab)
+        if feats is None:
+            static = dict(points=batch["points"].clone(), gt_bboxes_3d=gt, gt_labels_3d=lab)
+        else:
+            static = dict(points=batch["points"].clone(),
+                          img_features=(tok_static if tok_static is not None else
+                                        dict(feats, tokens=feats["tokens"].clone())
+                                        if isinstance(feats, dict) else [f.clone() for f in feats]),
+                          img_metas=batch["img_metas"], gt_bboxes_3d=gt, gt_labels_3d=lab)
         batch = static
         if head is not None and hasattr(head, "pin_metas"):
             head.pin_metas(static["img_metas"])     # the graph holds raw pointers into its cache entry
@@ -1016,9 +1023,14 @@ class Trainer:
             if can_prefetch and not skip_geo:
                 geo.ensure(torch.cuda.current_stream(), new["points"], static["points"])
             static["points"].copy_(new["points"])
-            nf = new["img_features"]
-            metas_done = False
-            if tok_static is not None and not isinstance(nf, dict):
+            if ("img_features" in new) != (feats is not None):
+                raise ValueError("load(): the captured step %s an image pyramid, the new batch %s"
+                                 % (("has", "has none") if feats is not None else ("has no", "brings one")))
+            nf = new.get("img_features")
+            metas_done = nf is None
+            if nf is None:
+                pass
+            elif tok_static is not None and not isinstance(nf, dict):
                 # the padding mask the conversion zeroes by is the NEW batch's: constants first
                 head.refresh_metas(static["img_metas"], new["img_metas"])
                 metas_done = True
@@ -1200,7 +1212,7 @@ class DoubleBufferedStep:
     (mmcv's DataLoader workers feeding MMDistributedDataParallel, /root/reference/train.py:140-147)."""
 
     def __init__(self, trainer, batch_a, batch_b, **kw):
-        if batch_a["img_metas"] is batch_b["img_metas"]:
+        if "img_features" in batch_a and batch_a["img_metas"] is batch_b["img_metas"]:
             raise ValueError("capture_double: the two batches must carry their own img_metas objects (each set of "
                              "static buffers owns the device constants cached for its metas)")
         self.trainer = trainer
@@ -1308,8 +1320,10 @@ class StepCache:
 
     @classmethod
     def key(cls, batch):
-        f = batch["img_features"]
-        if isinstance(f, dict):
+        f = batch.get("img_features")
+        if f is None:
+            img = None                             # a points-only batch: the pyramid is no part of the shape
+        elif isinstance(f, dict):
             img = (tuple(f["tokens"].shape), tuple(tuple(s) for s in f["spatial"]))
         else:
             img = tuple(tuple(t.shape) for t in f)

@@ -1,7 +1,7 @@
 """The test loop and its command line: what the reference's ``eval.py --eval mAP`` does (README.md:43-46).
 
   python -m demf_amd.infer --data-root R --ann-file sunrgbd_infos_val.pkl --checkpoint C
-                           [--batch-size 8] [--workers 8] [--out results.pkl] [--no-eval]
+                           [--batch-size 8] [--workers 8] [--out results.pkl] [--no-eval] [--model {demf,votenet}]
   python -m demf_amd.infer --data-root R --frames manifest.json --checkpoint C --out results.pkl
 
 ``--frames`` runs raw RGB-D frames (``dataset.RGBDFrames``: colour image, 16-bit depth PNG, calibration) through
@@ -28,8 +28,10 @@ def run_test(model, dataset, batch_size=8, workers=8, num_points=20000, img_scal
     or a new worst-case one).  The last batch may be smaller; there is no host sync inside the loop.  ``pipeline``:
     a test-mode pipeline instance for the loader to use (``FramePipeline`` for raw frames), which then brings its
     own ``num_points`` / ``img_scale`` / ``seed``."""
+    # (a model without an image stream - modules.VoteNet - is fed points alone: no image is read, decoded or uploaded)
     loader = SceneLoader(dataset, batch_size, "test", seed=seed, img_scale=img_scale, num_points=num_points,
-                         workers=workers, pipeline=pipeline)
+                         workers=workers, pipeline=pipeline,
+                         with_img=hasattr(model, "extract_img_feat") if pipeline is None else None)
     model.eval()
     if store is None:
         store = DetectionStore(max(len(dataset), 1), device=loader.device)
@@ -71,6 +73,8 @@ def parse_args(argv=None):
     p.add_argument("--workers", type=int, default=8)
     p.add_argument("--out", default=None, help="pickle the per-scene results (the reference's --out)")
     p.add_argument("--no-eval", action="store_true", help="do not evaluate (then --out is required)")
+    p.add_argument("--model", choices=("demf", "votenet"), default="demf",
+                   help="demf: DeMFVoteNet; votenet: the points-only class-agnostic baseline (modules.VoteNet)")
     args = p.parse_args(argv)
     if args.batch_size < 1 or args.workers < 1:
         p.error("--batch-size and --workers must be positive")
@@ -97,8 +101,8 @@ def main(argv=None, model=None, **loader_kwargs):
     else:
         dataset = SUNRGBDDataset(args.data_root, args.ann_file, test_mode=True)
     if model is None:
-        from .modules import DeMFVoteNet
-        model = DeMFVoteNet()
+        from .modules import DeMFVoteNet, VoteNet
+        model = VoteNet() if args.model == "votenet" else DeMFVoteNet()
     load_checkpoint(model, args.checkpoint)
     model.cuda()
     store = run_test(model, dataset, batch_size=args.batch_size, workers=args.workers, **loader_kwargs)

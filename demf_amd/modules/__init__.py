@@ -1,6 +1,7 @@
-from .coder import DeMFClassAgnosticBBoxCoder
-from .detector import DeMFHotPath, DeMFVoteNet, head_kwargs
-from .head import DeMFVoteHead
+from .ca_head import CAVoteHead
+from .coder import ClassAgnosticBBoxCoder, DeMFClassAgnosticBBoxCoder
+from .detector import DeMFHotPath, DeMFVoteNet, VoteNet, head_kwargs
+from .head import DeMFVoteHead, VoteHeadBase
 from .image_stream import ChannelMapper, DeformableDetrEncoder, ImageStream, ResNet50
 from .pointnet2 import PointFPModule, PointNet2SASSG, PointSAModule, build_sa_module
 from .transformer import (DeMFTransformerDecoderLayer, MultiScaleDeformableAttention,
@@ -11,4 +12,5 @@ __all__ = ["DeMFClassAgnosticBBoxCoder", "DeMFHotPath", "DeMFVoteNet", "head_kwa
            "PointFPModule", "PointNet2SASSG", "PointSAModule", "build_sa_module",
            "DeMFTransformerDecoderLayer", "MultiScaleDeformableAttention",
            "PositionEmbeddingLearned", "BaseConvBboxHead", "VoteModule", "ImageStream",
-           "ResNet50", "ChannelMapper", "DeformableDetrEncoder"]
+           "ResNet50", "ChannelMapper", "DeformableDetrEncoder", "CAVoteHead", "ClassAgnosticBBoxCoder", "VoteNet",
+           "VoteHeadBase"]

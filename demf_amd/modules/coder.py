@@ -147,3 +147,63 @@ class DeMFClassAgnosticBBoxCoder:
     def decode_corners(self, center, size):
         half = size / 2.0
         return torch.cat([center - half, center + half], dim=-1)
+
+
+class ClassAgnosticBBoxCoder(DeMFClassAgnosticBBoxCoder):
+    """The coder of the points-only class-agnostic VoteNet baseline (CAVoteHead) - mirrors
+    demf/core/bbox/coders/class_agnostic_bbox_coder.py:8-137.  A box is the six distances from a reference
+    point (the aggregated proposal point) to its faces in the box's own frame, predicted as their logarithms:
+    ``distance`` = exp(reg[..., 0:6]) = (front, left, top, back, right, bottom).  The angle helpers are the
+    inherited ones."""
+
+    # ---- :16-40 ----
+    def encode(self, gravity_center, dims, yaw, labels, ret_dir_target=False):
+        """As the DeMF coder's, except that the size target is HALF the box dimensions (:21)."""
+        out = super().encode(gravity_center, dims, yaw, labels, ret_dir_target)
+        return (out[0], dims / 2) + tuple(out[2:])
+
+    # ---- :42-86 ----
+    def decode(self, bbox_out, mode="rpn"):
+        assert mode == "rpn"
+        distance = bbox_out["distance"]
+        B, N, _ = distance.shape
+        if self.with_rot:
+            dir_class = torch.argmax(bbox_out["dir_class"], -1).detach()
+            dir_res = torch.gather(bbox_out["dir_res"], -1, dir_class.unsqueeze(-1)).squeeze(-1)
+            dir_angle = self.class2angle(dir_class, dir_res).reshape(B, N, 1)
+            dir_angle = dir_angle % (2 * np.pi)
+        else:
+            dir_angle = distance.new_zeros(B, N, 1)
+        bbox_size = torch.clamp(distance[..., 0:3] + distance[..., 3:6], min=0.1)
+        canonical_xyz = (distance[..., 3:6] - distance[..., 0:3]) / 2
+        from ..geometry import rotation_3d_in_axis_z
+        canonical_xyz = rotation_3d_in_axis_z(canonical_xyz.reshape(B * N, 1, 3),
+                                              dir_angle.reshape(B * N)).reshape(B, N, 3)
+        center = bbox_out["ref_points"] - canonical_xyz
+        return torch.cat([center, bbox_size, dir_angle], dim=-1)
+
+    # ---- :88-127 ----
+    def split_pred(self, cls_preds, reg_preds, ref_points):
+        results = _Preds()
+        cls_t = cls_preds.transpose(2, 1)
+        reg_t = reg_preds.transpose(2, 1)
+        nb = self.num_dir_bins
+        # "distance" = exp(reg[..., 0:6]) and "dir_res" = dir_res_norm * (pi / nb) are materialised on first
+        # access (see _Preds): the fused loss and decode kernels read the raw rows and compute both themselves
+        log_distance = reg_t[..., 0:6]
+        results.lazy["distance"] = lambda: log_distance.exp()
+        results.recipe["distance"] = (log_distance,)
+        results["dir_class"] = reg_t[..., 6:6 + nb]
+        dir_res_norm = reg_t[..., 6 + nb:6 + 2 * nb]
+        results["dir_res_norm"] = dir_res_norm
+        results.lazy["dir_res"] = lambda: dir_res_norm * (np.pi / nb)
+        results.recipe["dir_res"] = (dir_res_norm, np.pi / nb)
+        results["obj_scores"] = cls_t[..., 0:2]
+        if cls_t.shape[-1] > 2:
+            results["sem_scores"] = cls_t[..., 2:]
+        results["ref_points"] = ref_points
+        return results
+
+    # ---- :129-137 ----
+    def decode_corners(self, distance, ref_points):
+        return torch.cat([ref_points - distance[..., 3:6], ref_points + distance[..., 0:3]], dim=-1)

@@ -10,7 +10,8 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..config import DeMFCfg, head_kwargs
+from ..config import DeMFCfg, VoteNetCfg, head_kwargs, votenet_head_kwargs
+from .ca_head import CAVoteHead
 from .head import DeMFVoteHead
 from .pointnet2 import PointNet2SASSG
 
@@ -163,6 +164,92 @@ class DeMFVoteNet(DeMFHotPath):
                 m["batch_input_shape"] = tuple(_img.shape[-2:])
         return self.simple_test(points[0], img_metas[0], img[0],
                                 bboxes_2d=bboxes_2d[0] if bboxes_2d is not None else None, **kwargs)
+
+
+class VoteNet(nn.Module):
+    """The points-only class-agnostic VoteNet baseline of configs/baseline/votenet.py ("VoteNet*" in the
+    reference's results): PointNet2SASSG -> CAVoteHead, no image.  Entry points and attribute names
+    (``backbone``, ``bbox_head``) are those of mmdet3d's VoteNet detector ([dep-recall]: that class is not in
+    the reference tree), so its checkpoints load with the same keys.
+
+      forward_train(points, img_metas, gt_bboxes_3d, gt_labels_3d) -> dict of losses
+      simple_test(points, img_metas) -> list of dict(boxes_3d, scores_3d, labels_3d)
+      predict_into(store, points, img_metas): the same detections appended to a device-resident store
+      forward_test(points, img_metas)  (single-augmentation form)
+    """
+
+    def __init__(self, cfg: VoteNetCfg = None):
+        super().__init__()
+        self.cfg = cfg or VoteNetCfg()
+        b = self.cfg.backbone
+        self.backbone = PointNet2SASSG(
+            in_channels=b.in_channels, num_points=b.num_points, radius=b.radius,
+            num_samples=b.num_samples, sa_channels=b.sa_channels, fp_channels=b.fp_channels,
+            use_xyz=b.use_xyz, normalize_xyz=b.normalize_xyz)
+        self.bbox_head = CAVoteHead(**votenet_head_kwargs(self.cfg))
+
+    def _sample_mod(self):
+        h = self.cfg.head
+        return h.train_sample_mod if self.training else h.test_sample_mod
+
+    @torch.no_grad()
+    def index_geometry(self, points):
+        """Coordinate-only pre-pass of the step, as DeMFHotPath.index_geometry."""
+        if isinstance(points, (list, tuple)):
+            points = torch.stack(points)
+        geo = self.backbone.index_geometry(points)
+        bb = self.backbone
+        seed_xyz = ([points[..., :3]] + [t[1] for t in geo["sa"]])[bb.num_sa - bb.num_fp]
+        if self._sample_mod() == "seed":
+            geo["sample_indices"] = ops.furthest_point_sample(seed_xyz.contiguous(), self.bbox_head.num_proposal)
+        return geo
+
+    def forward_head(self, points, geometry=None):
+        if isinstance(points, (list, tuple)):
+            points = torch.stack(points)
+        x = self.backbone(points, geometry)
+        feat_dict = dict(seed_points=x["fp_xyz"][-1], seed_features=x["fp_features"][-1],
+                         seed_indices=x["fp_indices"][-1],
+                         sample_indices=None if geometry is None else geometry.get("sample_indices"))
+        return self.bbox_head(feat_dict, self._sample_mod())
+
+    def forward_train(self, points=None, img_metas=None, gt_bboxes_3d=None, gt_labels_3d=None, geometry=None,
+                      **unused):
+        if isinstance(points, (list, tuple)):
+            points = torch.stack(points)
+        bbox_preds = self.forward_head(points, geometry)
+        return self.bbox_head.loss(bbox_preds, points, gt_bboxes_3d, gt_labels_3d, None, None, img_metas)
+
+    def param_groups(self, lr=0.008, weight_decay=0.01):
+        """One AdamW group (configs/_base_/schedules/schedule_3x.py:6): the baseline has no decoder group."""
+        return [dict(params=[p for p in self.parameters() if p.requires_grad], lr=lr, weight_decay=weight_decay)]
+
+    @torch.no_grad()
+    def simple_test(self, points=None, img_metas=None, rescale=False, **unused):
+        if isinstance(points, (list, tuple)):
+            points = torch.stack(points)
+        bbox_preds = self.forward_head(points)
+        return self.bbox_head.get_bboxes_packed(points, bbox_preds, img_metas).results()
+
+    @torch.no_grad()
+    def predict_into(self, store, points=None, img_metas=None, **unused):
+        """``simple_test`` whose detections stay on the device (detections.DetectionStore); no host sync."""
+        if isinstance(points, (list, tuple)):
+            points = torch.stack(points)
+        bbox_preds = self.forward_head(points)
+        self.bbox_head.get_bboxes_packed(points, bbox_preds, img_metas, store)
+
+    def forward_test(self, points=None, img_metas=None, **kwargs):
+        for var, name in ((points, "points"), (img_metas, "img_metas")):
+            if not isinstance(var, list):
+                raise TypeError("{} must be a list, but got {}".format(name, type(var)))
+        if len(points) != len(img_metas):
+            raise ValueError("num of augmentations ({}) != num of image meta ({})".format(
+                len(points), len(img_metas)))
+        if len(points) != 1:
+            raise NotImplementedError("test-time augmentation is not implemented")
+        kwargs.pop("img", None)
+        return self.simple_test(points[0], img_metas[0], **kwargs)
 
 
 def bbox3d2result(bboxes, scores, labels):

@@ -73,7 +73,219 @@ def compose_projection(img_meta):
     return M, au / (img_w - 1), bu / (img_w - 1), av / (img_h - 1), bv / (img_h - 1)
 
 
-class DeMFVoteHead(nn.Module):
+class VoteHeadBase(nn.Module):
+    """What the two vote heads of the reference share (DeMFVoteHead and the points-only CAVoteHead, both in
+    class_agnostic_vote_head.py): ground-truth padding, the batched target generation, and the test-time tail
+    behind the decode (point count, NMS, packing).  The line numbers cited are DeMFVoteHead's; CAVoteHead's
+    get_targets / get_targets_single (:123-316) compute the same quantities."""
+
+    @torch.no_grad()
+    def _nms_pack(self, points, decoded, store=None):
+        """The tail of ``get_bboxes_packed`` behind the decode: ``decoded`` = (box7, cos_yaw, sin_yaw, obj, sem,
+        classes) of ops.detect_decode / ops.ca_detect_decode -> the store."""
+        from ..detections import DetectionStore
+        tc = self.test_cfg
+        box7, cosy, siny, obj, sem, classes = decoded
+        if isinstance(points, (list, tuple)):
+            points = torch.stack(points)
+        bottom, extent, count = ops.box_extent_count(points.contiguous(), box7, (cosy, siny))
+        keep = ops.aligned_nms(extent, obj, classes, count > 5, tc["nms_thr"], as_bytes=True)
+        B, K, C = sem.shape
+        per_class = bool(tc["per_class_proposal"])
+        if store is None:
+            store = DetectionStore(max(B, 1), device=sem.device)
+        first = store.reserve(B, K * (C if per_class else 1))
+        ops.detect_pack(keep, obj, sem, classes, bottom, tc["score_thr"], per_class, first, store.boxes,
+                        store.scores, store.labels, store.scene_off, store.state)
+        return store
+
+    def _unpack(self, store, input_metas):
+        """A batch's store -> the reference's list of (boxes, scores, labels) per scene: one host sync."""
+        off, rows = store.host_index()
+        labels = store.labels[:rows].to(torch.int64)
+        results = []
+        for b, (lo, hi) in enumerate(zip(off[:-1].tolist(), off[1:].tolist())):
+            bx = store.boxes[lo:hi]
+            wrap = input_metas[b].get("box_type_3d") if input_metas is not None else None
+            results.append((wrap(bx, box_dim=bx.shape[-1], with_yaw=self.bbox_coder.with_rot)
+                            if wrap is not None else DepthBoxes(bx), store.scores[lo:hi], labels[lo:hi]))
+        return results
+
+    # ---- targets: :756-941, batched ----------------------------------------------
+    _PAD_CACHE = {}
+
+    @staticmethod
+    def pad_gt(gt_bboxes_3d, gt_labels_3d, device, with_slot_labels=False, G=None):
+        """list[DepthBoxes|(n,7) tensor], list[(n,) long] -> padded (B,G,7), (B,G), valid (B,G).
+        An empty scene gets the reference's single all-zero fake box (:766-773).
+        One concatenation + one row gather per tensor: the rows are [0-row | all boxes] and
+        [-1, 0 | all labels]; the slot -> row table and the valid mask depend only on the per-scene
+        counts and are cached per count signature.  ``with_slot_labels``: the labels keep -1 in the
+        padding slots (the form ``ops.gt_prep`` reads ``valid`` from) instead of 0."""
+        boxes = [b.tensor if isinstance(b, DepthBoxes) else b for b in gt_bboxes_3d]
+        counts = tuple(int(b.shape[0]) for b in boxes)
+        if G is None:
+            G = max(1, max(counts))                      # (a captured step passes its static slot count)
+        elif max(counts) > G:
+            raise ValueError(f"a scene has {max(counts)} ground-truth boxes, the padded form holds {G}")
+        B = len(boxes)
+        if B <= 32 and torch.device(device).type == "cuda" and all(b.is_cuda for b in boxes) \
+                and all(l.is_cuda for l in gt_labels_3d):
+            # device lists: ONE launch, pointers + counts by value in the kernel arguments - no index
+            # tables, no host -> device copy whatever the per-scene counts are (ops.pad_gt_lists)
+            gt, slot, valid = ops.pad_gt_lists(boxes, gt_labels_3d, G)
+            if with_slot_labels:
+                return gt, slot, valid
+            return gt, slot.clamp_(min=0), valid
+        key = (counts, G, str(device))
+        cache = VoteHeadBase._PAD_CACHE
+        if key not in cache:
+            if len(cache) > 64:
+                cache.clear()
+            valid = np.zeros((B, G), dtype=bool)
+            box_row = np.zeros((B, G), dtype=np.int64)          # row 0 of the box rows: zeros
+            lab_row = np.zeros((B, G), dtype=np.int64)          # row 0 of the label rows: -1 (padding)
+            at = 0
+            for i, n in enumerate(counts):
+                valid[i, :max(n, 1)] = True
+                box_row[i, :n] = 1 + at + np.arange(n)
+                lab_row[i, :n] = 2 + at + np.arange(n)
+                if n == 0:
+                    lab_row[i, 0] = 1                           # row 1: label 0 of the fake box
+                at += n
+            cache[key] = (torch.as_tensor(box_row.reshape(-1), device=device),
+                          torch.as_tensor(lab_row.reshape(-1), device=device),
+                          torch.as_tensor(valid, device=device),
+                          torch.zeros((1, 7), dtype=torch.float32, device=device),
+                          torch.tensor([-1, 0], dtype=torch.long, device=device))
+        box_row, lab_row, valid, zero_row, lab_head = cache[key]
+        gt = torch.cat([zero_row] + [b.to(device).float() for b in boxes if b.shape[0]]).index_select(0, box_row)
+        slot = torch.cat([lab_head] + [l.to(device) for l, n in zip(gt_labels_3d, counts) if n]) \
+            .index_select(0, lab_row).view(B, G)
+        if with_slot_labels:
+            return gt.view(B, G, 7), slot, valid
+        return gt.view(B, G, 7), slot.clamp_(min=0), valid
+
+    @torch.no_grad()
+    def vote_targets(self, points, gt_bboxes_3d, gt_labels_3d):
+        """The proposal-independent half of get_targets (:828-858): per-point vote targets from
+        box membership (first / second / last containing box).  Only needs the inputs, so the
+        detector computes it on a side stream.  -> dict incl. the padded GT."""
+        if isinstance(points, (list, tuple)):
+            points = torch.stack(points)
+        if isinstance(gt_bboxes_3d, (list, tuple)) and points.is_cuda:
+            # per-scene lists on the device: pad to (B,G,7) / (B,G) with -1 in the padding slots and
+            # take the padded path below (2 x (cat + row gather), then gt_prep + vote_targets_k)
+            gt_bboxes_3d, gt_labels_3d, _ = self.pad_gt(gt_bboxes_3d, gt_labels_3d, points.device,
+                                                        with_slot_labels=True)
+        if isinstance(gt_bboxes_3d, (list, tuple)):
+            gt, lab, valid = self.pad_gt(gt_bboxes_3d, gt_labels_3d, points.device)
+        else:
+            # already padded (B,G,7) / (B,G): label -1 marks a padding slot (static-shape loops)
+            gt = gt_bboxes_3d
+            if gt.is_cuda and gt.is_contiguous() and gt_labels_3d.is_contiguous() and \
+                    gt_labels_3d.dtype == torch.int64 and points.is_contiguous() and gt.shape[1] <= 64:
+                # device path of the captured step: the GT-only quantities (cos / sin(-yaw),
+                # angle2class, valid, clamped labels, gravity centres) in one launch, then
+                # vote_targets_k; the torch code below is the specification of both
+                prep = ops.gt_prep(gt, gt_labels_3d, self.num_dir_bins)
+                vote_targets, masks = ops.vote_targets(points, gt, prep["valid"], prep=prep)
+                return dict(gt=gt, lab=prep["lab"], valid=prep["valid"], center=prep["center"],
+                            dims=gt[..., 3:6], yaw=gt[..., 6], vote_targets=vote_targets,
+                            vote_target_masks=masks, prep=prep)
+            valid = gt_labels_3d >= 0
+            lab = gt_labels_3d.clamp(min=0)
+        B, G = gt.shape[:2]
+        p = points[..., :3]
+        center = torch.cat([gt[..., :2], gt[..., 2:3] + gt[..., 5:6] * 0.5], dim=-1)  # gravity
+        dims, yaw = gt[..., 3:6], gt[..., 6]
+        if points.is_cuda and G <= 64 and points.is_contiguous() and gt.is_contiguous():
+            # one kernel (csrc/loss.hip: vote_targets_k) instead of ~45 broadcast kernels; the torch
+            # code below is its specification (and what the CPU golden tests run)
+            vote_targets, masks = ops.vote_targets(points, gt, valid)
+            return dict(gt=gt, lab=lab, valid=valid, center=center, dims=dims, yaw=yaw,
+                        vote_targets=vote_targets, vote_target_masks=masks)
+        rel = p[:, :, None, :] - center[:, None, :, :]                        # (B,N,G,3)
+        cs, sn = torch.cos(-yaw)[:, None], torch.sin(-yaw)[:, None]
+        lx = rel[..., 0] * cs + rel[..., 1] * sn
+        ly = -rel[..., 0] * sn + rel[..., 1] * cs
+        half = dims[:, None] * 0.5
+        inb = (rel[..., 2].abs() <= half[..., 2]) & (lx.abs() < half[..., 0]) & \
+              (ly.abs() < half[..., 1]) & valid[:, None, :]
+        # running count of containing boxes: a (G,G) triangular matmul instead of an int64 scan
+        tri = torch.triu(torch.ones(G, G, dtype=p.dtype, device=p.device))
+        cnt = torch.matmul(inb.to(p.dtype), tri).round().long()
+        total = cnt[..., -1:]
+        votes = -rel                                                          # centre - point
+        pick = lambda m: (votes * m.unsqueeze(-1).to(votes.dtype)).sum(2)
+        v1 = pick(inb & (cnt == 1))
+        v2 = pick(inb & (cnt == 2))
+        vl = pick(inb & (cnt == total))
+        s1 = torch.where(total >= 2, v2, v1)
+        s2 = torch.where(total >= 3, vl, v1)
+        has = total > 0
+        vote_targets = torch.cat([v1, s1, s2], dim=-1) * has.to(votes.dtype)
+        return dict(gt=gt, lab=lab, valid=valid, center=center, dims=dims, yaw=yaw,
+                    vote_targets=vote_targets, vote_target_masks=has.squeeze(-1).long())
+
+    @torch.no_grad()
+    def get_targets(self, points, gt_bboxes_3d, gt_labels_3d, bbox_preds, vote_pack=None):
+        vp = vote_pack if vote_pack is not None else \
+            self.vote_targets(points, gt_bboxes_3d, gt_labels_3d)
+        lab, valid, center, dims, yaw = vp["lab"], vp["valid"], vp["center"], vp["dims"], vp["yaw"]
+        vote_targets, vote_target_masks = vp["vote_targets"], vp["vote_target_masks"]
+        agg = bbox_preds["aggregated_points"]
+
+        # -- proposal targets (:877-934)
+        prep = vp.get("prep")
+        if prep is not None:
+            dir_class_t, dir_res_t = prep["dir_class"], prep["dir_res"]
+        else:
+            dir_class_t, dir_res_t = self.bbox_coder.angle2class(yaw)
+        pos_thr = self.train_cfg["pos_distance_thr"]
+        neg_thr = self.train_cfg["neg_distance_thr"]
+        if agg.is_cuda and "gt" in vp and vp["gt"].is_contiguous():
+            # one kernel (csrc/loss.hip: proposal_targets_k); the torch code below is its spec
+            t = ops.proposal_targets(agg.contiguous(), vp["gt"], lab, valid, dir_class_t, dir_res_t,
+                                     self.bbox_coder.with_rot, pos_thr, neg_thr,
+                                     np.pi / self.num_dir_bins, prep=prep)
+            objectness_masks, objectness_targets = t["objectness_masks"], t["objectness"]
+            objectness_weights, box_loss_weights = ops.target_weights(objectness_masks,
+                                                                      objectness_targets)
+            return (vote_targets, vote_target_masks, t["dir_class"], t["dir_res"], t["mask"],
+                    objectness_targets, objectness_weights, box_loss_weights, t["distance"],
+                    t["dir"], t["size"], t["center"])
+        d = ((agg[:, :, None, :] - center[:, None, :, :]) ** 2).sum(-1)       # (B,Q,G) mse-sum
+        d = d.masked_fill(~valid[:, None, :], float("inf"))
+        distance1, assignment = d.min(-1)
+        euc = torch.sqrt(distance1 + 1e-6)
+        objectness_masks = ((euc < pos_thr) | (euc > neg_thr)).to(agg.dtype)
+        g3 = assignment.unsqueeze(-1).expand(-1, -1, 3)
+        center_targets = torch.gather(center, 1, g3)
+        size_targets = torch.gather(dims, 1, g3)
+        dir_class_targets = torch.gather(dir_class_t, 1, assignment)
+        dir_res_targets = torch.gather(dir_res_t, 1, assignment) / (np.pi / self.num_dir_bins)
+        dir_targets = torch.gather(yaw, 1, assignment)
+        mask_targets = torch.gather(lab, 1, assignment).long()
+        canonical = agg - center_targets
+        if self.bbox_coder.with_rot:
+            Bq = canonical.shape[0] * canonical.shape[1]
+            canonical = rotation_3d_in_axis_z(canonical.reshape(Bq, 1, 3),
+                                              -dir_targets.reshape(Bq)).reshape(agg.shape)
+        half_t = size_targets / 2.0
+        distance_targets = torch.cat([half_t - canonical, half_t + canonical], dim=-1)
+        inside = (distance_targets >= 0.0).all(dim=-1)
+        objectness_targets = ((euc < pos_thr) & inside).long()
+
+        # -- batch normalisation of weights (:797-816)
+        objectness_weights = objectness_masks / (objectness_masks.sum() + 1e-6)
+        box_loss_weights = objectness_targets.float() / (objectness_targets.sum().float() + 1e-6)
+        return (vote_targets, vote_target_masks, dir_class_targets, dir_res_targets, mask_targets,
+                objectness_targets, objectness_weights, box_loss_weights, distance_targets,
+                dir_targets, size_targets, center_targets)
+
+
+class DeMFVoteHead(VoteHeadBase):
     def __init__(self, num_classes, bbox_coder, train_cfg=None, test_cfg=None,
                  vote_module_cfg=None, vote_aggregation_cfg=None, pred_layer_cfg=None,
                  conv_cfg=None, norm_cfg=None, objectness_loss=None, center_loss=None,
@@ -598,22 +810,8 @@ class DeMFVoteHead(nn.Module):
         csrc/detect.hip and csrc/postprocess.hip around one ``count > 5`` mask.  No launch has a shape that
         depends on data and nothing synchronises with the host; the batch's scenes are appended to ``store`` in
         order, rows in the reference's order.  -> the store."""
-        from ..detections import DetectionStore
-        tc = self.test_cfg
-        box7, cosy, siny, obj, sem, classes = ops.detect_decode(
-            self._decode_layers(bbox_preds), self.num_dir_bins, self.bbox_coder.with_rot)
-        if isinstance(points, (list, tuple)):
-            points = torch.stack(points)
-        bottom, extent, count = ops.box_extent_count(points.contiguous(), box7, (cosy, siny))
-        keep = ops.aligned_nms(extent, obj, classes, count > 5, tc["nms_thr"], as_bytes=True)
-        B, K, C = sem.shape
-        per_class = bool(tc["per_class_proposal"])
-        if store is None:
-            store = DetectionStore(max(B, 1), device=sem.device)
-        first = store.reserve(B, K * (C if per_class else 1))
-        ops.detect_pack(keep, obj, sem, classes, bottom, tc["score_thr"], per_class, first, store.boxes,
-                        store.scores, store.labels, store.scene_off, store.state)
-        return store
+        decoded = ops.detect_decode(self._decode_layers(bbox_preds), self.num_dir_bins, self.bbox_coder.with_rot)
+        return self._nms_pack(points, decoded, store)
 
     @torch.no_grad()
     def get_bboxes(self, points, bbox_preds, input_metas, rescale=False, use_nms=True):
@@ -626,186 +824,4 @@ class DeMFVoteHead(nn.Module):
         if not use_nms:
             return ops.detect_decode(self._decode_layers(bbox_preds), self.num_dir_bins,
                                      self.bbox_coder.with_rot)[0]
-        store = self.get_bboxes_packed(points, bbox_preds, input_metas)
-        off, rows = store.host_index()
-        labels = store.labels[:rows].to(torch.int64)
-        results = []
-        for b, (lo, hi) in enumerate(zip(off[:-1].tolist(), off[1:].tolist())):
-            bx = store.boxes[lo:hi]
-            wrap = input_metas[b].get("box_type_3d") if input_metas is not None else None
-            results.append((wrap(bx, box_dim=bx.shape[-1], with_yaw=self.bbox_coder.with_rot)
-                            if wrap is not None else DepthBoxes(bx), store.scores[lo:hi], labels[lo:hi]))
-        return results
-
-    # ---- targets: :756-941, batched ----------------------------------------------
-    _PAD_CACHE = {}
-
-    @staticmethod
-    def pad_gt(gt_bboxes_3d, gt_labels_3d, device, with_slot_labels=False, G=None):
-        """list[DepthBoxes|(n,7) tensor], list[(n,) long] -> padded (B,G,7), (B,G), valid (B,G).
-        An empty scene gets the reference's single all-zero fake box (:766-773).
-        One concatenation + one row gather per tensor: the rows are [0-row | all boxes] and
-        [-1, 0 | all labels]; the slot -> row table and the valid mask depend only on the per-scene
-        counts and are cached per count signature.  ``with_slot_labels``: the labels keep -1 in the
-        padding slots (the form ``ops.gt_prep`` reads ``valid`` from) instead of 0."""
-        boxes = [b.tensor if isinstance(b, DepthBoxes) else b for b in gt_bboxes_3d]
-        counts = tuple(int(b.shape[0]) for b in boxes)
-        if G is None:
-            G = max(1, max(counts))                      # (a captured step passes its static slot count)
-        elif max(counts) > G:
-            raise ValueError(f"a scene has {max(counts)} ground-truth boxes, the padded form holds {G}")
-        B = len(boxes)
-        if B <= 32 and torch.device(device).type == "cuda" and all(b.is_cuda for b in boxes) \
-                and all(l.is_cuda for l in gt_labels_3d):
-            # device lists: ONE launch, pointers + counts by value in the kernel arguments - no index
-            # tables, no host -> device copy whatever the per-scene counts are (ops.pad_gt_lists)
-            gt, slot, valid = ops.pad_gt_lists(boxes, gt_labels_3d, G)
-            if with_slot_labels:
-                return gt, slot, valid
-            return gt, slot.clamp_(min=0), valid
-        key = (counts, G, str(device))
-        cache = DeMFVoteHead._PAD_CACHE
-        if key not in cache:
-            if len(cache) > 64:
-                cache.clear()
-            valid = np.zeros((B, G), dtype=bool)
-            box_row = np.zeros((B, G), dtype=np.int64)          # row 0 of the box rows: zeros
-            lab_row = np.zeros((B, G), dtype=np.int64)          # row 0 of the label rows: -1 (padding)
-            at = 0
-            for i, n in enumerate(counts):
-                valid[i, :max(n, 1)] = True
-                box_row[i, :n] = 1 + at + np.arange(n)
-                lab_row[i, :n] = 2 + at + np.arange(n)
-                if n == 0:
-                    lab_row[i, 0] = 1                           # row 1: label 0 of the fake box
-                at += n
-            cache[key] = (torch.as_tensor(box_row.reshape(-1), device=device),
-                          torch.as_tensor(lab_row.reshape(-1), device=device),
-                          torch.as_tensor(valid, device=device),
-                          torch.zeros((1, 7), dtype=torch.float32, device=device),
-                          torch.tensor([-1, 0], dtype=torch.long, device=device))
-        box_row, lab_row, valid, zero_row, lab_head = cache[key]
-        gt = torch.cat([zero_row] + [b.to(device).float() for b in boxes if b.shape[0]]).index_select(0, box_row)
-        slot = torch.cat([lab_head] + [l.to(device) for l, n in zip(gt_labels_3d, counts) if n]) \
-            .index_select(0, lab_row).view(B, G)
-        if with_slot_labels:
-            return gt.view(B, G, 7), slot, valid
-        return gt.view(B, G, 7), slot.clamp_(min=0), valid
-
-    @torch.no_grad()
-    def vote_targets(self, points, gt_bboxes_3d, gt_labels_3d):
-        """The proposal-independent half of get_targets (:828-858): per-point vote targets from
-        box membership (first / second / last containing box).  Only needs the inputs, so the
-        detector computes it on a side stream.  -> dict incl. the padded GT."""
-        if isinstance(points, (list, tuple)):
-            points = torch.stack(points)
-        if isinstance(gt_bboxes_3d, (list, tuple)) and points.is_cuda:
-            # per-scene lists on the device: pad to (B,G,7) / (B,G) with -1 in the padding slots and
-            # take the padded path below (2 x (cat + row gather), then gt_prep + vote_targets_k)
-            gt_bboxes_3d, gt_labels_3d, _ = self.pad_gt(gt_bboxes_3d, gt_labels_3d, points.device,
-                                                        with_slot_labels=True)
-        if isinstance(gt_bboxes_3d, (list, tuple)):
-            gt, lab, valid = self.pad_gt(gt_bboxes_3d, gt_labels_3d, points.device)
-        else:
-            # already padded (B,G,7) / (B,G): label -1 marks a padding slot (static-shape loops)
-            gt = gt_bboxes_3d
-            if gt.is_cuda and gt.is_contiguous() and gt_labels_3d.is_contiguous() and \
-                    gt_labels_3d.dtype == torch.int64 and points.is_contiguous() and gt.shape[1] <= 64:
-                # device path of the captured step: the GT-only quantities (cos / sin(-yaw),
-                # angle2class, valid, clamped labels, gravity centres) in one launch, then
-                # vote_targets_k; the torch code below is the specification of both
-                prep = ops.gt_prep(gt, gt_labels_3d, self.num_dir_bins)
-                vote_targets, masks = ops.vote_targets(points, gt, prep["valid"], prep=prep)
-                return dict(gt=gt, lab=prep["lab"], valid=prep["valid"], center=prep["center"],
-                            dims=gt[..., 3:6], yaw=gt[..., 6], vote_targets=vote_targets,
-                            vote_target_masks=masks, prep=prep)
-            valid = gt_labels_3d >= 0
-            lab = gt_labels_3d.clamp(min=0)
-        B, G = gt.shape[:2]
-        p = points[..., :3]
-        center = torch.cat([gt[..., :2], gt[..., 2:3] + gt[..., 5:6] * 0.5], dim=-1)  # gravity
-        dims, yaw = gt[..., 3:6], gt[..., 6]
-        if points.is_cuda and G <= 64 and points.is_contiguous() and gt.is_contiguous():
-            # one kernel (csrc/loss.hip: vote_targets_k) instead of ~45 broadcast kernels; the torch
-            # code below is its specification (and what the CPU golden tests run)
-            vote_targets, masks = ops.vote_targets(points, gt, valid)
-            return dict(gt=gt, lab=lab, valid=valid, center=center, dims=dims, yaw=yaw,
-                        vote_targets=vote_targets, vote_target_masks=masks)
-        rel = p[:, :, None, :] - center[:, None, :, :]                        # (B,N,G,3)
-        cs, sn = torch.cos(-yaw)[:, None], torch.sin(-yaw)[:, None]
-        lx = rel[..., 0] * cs + rel[..., 1] * sn
-        ly = -rel[..., 0] * sn + rel[..., 1] * cs
-        half = dims[:, None] * 0.5
-        inb = (rel[..., 2].abs() <= half[..., 2]) & (lx.abs() < half[..., 0]) & \
-              (ly.abs() < half[..., 1]) & valid[:, None, :]
-        # running count of containing boxes: a (G,G) triangular matmul instead of an int64 scan
-        tri = torch.triu(torch.ones(G, G, dtype=p.dtype, device=p.device))
-        cnt = torch.matmul(inb.to(p.dtype), tri).round().long()
-        total = cnt[..., -1:]
-        votes = -rel                                                          # centre - point
-        pick = lambda m: (votes * m.unsqueeze(-1).to(votes.dtype)).sum(2)
-        v1 = pick(inb & (cnt == 1))
-        v2 = pick(inb & (cnt == 2))
-        vl = pick(inb & (cnt == total))
-        s1 = torch.where(total >= 2, v2, v1)
-        s2 = torch.where(total >= 3, vl, v1)
-        has = total > 0
-        vote_targets = torch.cat([v1, s1, s2], dim=-1) * has.to(votes.dtype)
-        return dict(gt=gt, lab=lab, valid=valid, center=center, dims=dims, yaw=yaw,
-                    vote_targets=vote_targets, vote_target_masks=has.squeeze(-1).long())
-
-    @torch.no_grad()
-    def get_targets(self, points, gt_bboxes_3d, gt_labels_3d, bbox_preds, vote_pack=None):
-        vp = vote_pack if vote_pack is not None else \
-            self.vote_targets(points, gt_bboxes_3d, gt_labels_3d)
-        lab, valid, center, dims, yaw = vp["lab"], vp["valid"], vp["center"], vp["dims"], vp["yaw"]
-        vote_targets, vote_target_masks = vp["vote_targets"], vp["vote_target_masks"]
-        agg = bbox_preds["aggregated_points"]
-
-        # -- proposal targets (:877-934)
-        prep = vp.get("prep")
-        if prep is not None:
-            dir_class_t, dir_res_t = prep["dir_class"], prep["dir_res"]
-        else:
-            dir_class_t, dir_res_t = self.bbox_coder.angle2class(yaw)
-        pos_thr = self.train_cfg["pos_distance_thr"]
-        neg_thr = self.train_cfg["neg_distance_thr"]
-        if agg.is_cuda and "gt" in vp and vp["gt"].is_contiguous():
-            # one kernel (csrc/loss.hip: proposal_targets_k); the torch code below is its spec
-            t = ops.proposal_targets(agg.contiguous(), vp["gt"], lab, valid, dir_class_t, dir_res_t,
-                                     self.bbox_coder.with_rot, pos_thr, neg_thr,
-                                     np.pi / self.num_dir_bins, prep=prep)
-            objectness_masks, objectness_targets = t["objectness_masks"], t["objectness"]
-            objectness_weights, box_loss_weights = ops.target_weights(objectness_masks,
-                                                                      objectness_targets)
-            return (vote_targets, vote_target_masks, t["dir_class"], t["dir_res"], t["mask"],
-                    objectness_targets, objectness_weights, box_loss_weights, t["distance"],
-                    t["dir"], t["size"], t["center"])
-        d = ((agg[:, :, None, :] - center[:, None, :, :]) ** 2).sum(-1)       # (B,Q,G) mse-sum
-        d = d.masked_fill(~valid[:, None, :], float("inf"))
-        distance1, assignment = d.min(-1)
-        euc = torch.sqrt(distance1 + 1e-6)
-        objectness_masks = ((euc < pos_thr) | (euc > neg_thr)).to(agg.dtype)
-        g3 = assignment.unsqueeze(-1).expand(-1, -1, 3)
-        center_targets = torch.gather(center, 1, g3)
-        size_targets = torch.gather(dims, 1, g3)
-        dir_class_targets = torch.gather(dir_class_t, 1, assignment)
-        dir_res_targets = torch.gather(dir_res_t, 1, assignment) / (np.pi / self.num_dir_bins)
-        dir_targets = torch.gather(yaw, 1, assignment)
-        mask_targets = torch.gather(lab, 1, assignment).long()
-        canonical = agg - center_targets
-        if self.bbox_coder.with_rot:
-            Bq = canonical.shape[0] * canonical.shape[1]
-            canonical = rotation_3d_in_axis_z(canonical.reshape(Bq, 1, 3),
-                                              -dir_targets.reshape(Bq)).reshape(agg.shape)
-        half_t = size_targets / 2.0
-        distance_targets = torch.cat([half_t - canonical, half_t + canonical], dim=-1)
-        inside = (distance_targets >= 0.0).all(dim=-1)
-        objectness_targets = ((euc < pos_thr) & inside).long()
-
-        # -- batch normalisation of weights (:797-816)
-        objectness_weights = objectness_masks / (objectness_masks.sum() + 1e-6)
-        box_loss_weights = objectness_targets.float() / (objectness_targets.sum().float() + 1e-6)
-        return (vote_targets, vote_target_masks, dir_class_targets, dir_res_targets, mask_targets,
-                objectness_targets, objectness_weights, box_loss_weights, distance_targets,
-                dir_targets, size_targets, center_targets)
+        return self._unpack(self.get_bboxes_packed(points, bbox_preds, input_metas), input_metas)

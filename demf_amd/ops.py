@@ -1767,6 +1767,67 @@ def head_loss(cls_rows, reg_rows, base_xyz, hyper12, center_t, size_t, dir_class
                            dir_res_t, sem_t, obj_t, obj_w, box_w)
 
 
+class _CAHeadLoss(Function):
+    @staticmethod
+    def forward(ctx, cls_rows, reg_rows, ref, hyper, distance_t, dir_class_t, dir_res_t, sem_t, obj_t, obj_w, box_w,
+                dir_t):
+        floats = [(cls_rows, "cls"), (reg_rows, "reg"), (distance_t, "distance_t"), (dir_res_t, "dir_res_t"),
+                  (obj_w, "obj_w"), (box_w, "box_w")]
+        floats += [(t, n) for t, n in ((ref, "ref_points"), (dir_t, "dir_t")) if t is not None]
+        for t, n in floats:
+            _chk(t, n)
+        for t, n in ((dir_class_t, "dir_class_t"), (sem_t, "sem_t"), (obj_t, "obj_t")):
+            _chk(t, n, torch.int64)
+        R = cls_rows.shape[0]
+        want = dict(cls=(cls_rows, (R, 12)), reg=(reg_rows, (R, 30)), distance_t=(distance_t, (R, 6)),
+                    dir_class_t=(dir_class_t, (R,)), dir_res_t=(dir_res_t, (R,)), sem_t=(sem_t, (R,)),
+                    obj_t=(obj_t, (R,)), obj_w=(obj_w, (R,)), box_w=(box_w, (R,)))
+        if ref is not None:
+            want["ref_points"] = (ref, (R, 3))
+        if dir_t is not None:
+            want["dir_t"] = (dir_t, (R,))
+        for n, (t, shape) in want.items():          # the kernels read (and write) R rows of every array
+            if tuple(t.shape) != shape:
+                raise ValueError(f"ca_head_loss: {n} must be {shape}, got {tuple(t.shape)}")
+        hp = (_ct.c_float * 12)(*hyper)
+        out = zeros(7, cls_rows.device)
+        _ffi.call("demf_ca_head_loss_fwd", R, 12, 10, hp, _p(cls_rows), _p(reg_rows), _p(distance_t),
+                  _p(dir_class_t), _p(dir_res_t), _p(sem_t), _p(obj_t), _p(obj_w), _p(box_w), _p(out), _stream())
+        saved = (cls_rows, reg_rows, distance_t, dir_class_t, dir_res_t, sem_t, obj_t, obj_w, box_w)
+        ctx.save_for_backward(*saved, *(() if dir_t is None else (dir_t,)))
+        ctx.hyper, ctx.with_dir = tuple(hyper), dir_t is not None
+        ctx.with_ref = ref is not None
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        cls_rows, reg_rows = ctx.saved_tensors[:2]
+        rest = ctx.saved_tensors[2:9]
+        dir_t = ctx.saved_tensors[9] if ctx.with_dir else None
+        R = cls_rows.shape[0]
+        hp = (_ct.c_float * 12)(*ctx.hyper)
+        gout = grad_out.contiguous()
+        gc, gr = torch.empty_like(cls_rows), torch.empty_like(reg_rows)
+        gref = torch.empty((R, 3), dtype=torch.float32, device=cls_rows.device) \
+            if ctx.with_ref and ctx.needs_input_grad[2] else None
+        _ffi.call("demf_ca_head_loss_bwd", R, 12, 10, hp, _p(cls_rows), _p(reg_rows), *[_p(t) for t in rest],
+                  _p(gout), _p(dir_t), _p(gc), _p(gr), _p(gref), _stream())
+        return (gc, gr, gref) + (None,) * 9
+
+
+def ca_head_loss(cls_rows, reg_rows, hyper12, distance_t, dir_class_t, dir_res_t, sem_t, obj_t, obj_w, box_w,
+                 ref_points=None, dir_t=None):
+    """The distance form of ``head_loss`` (CAVoteHead.loss, see demf_ca_head_loss_fwd): reg rows hold the log of the
+    six face distances, ``distance_t`` (R,6) comes unclamped from ``proposal_targets``.  -> (7,) in HEAD_LOSS_NAMES
+    order with an exact 0 in the ``center_loss`` slot; ``hyper12`` as for ``head_loss`` (its two centre entries are
+    not read).  The loss VALUE does not depend on the reference points; with ``ref_points`` (R,3) given they receive
+    the gradient the reference sends them through the distance targets, which it builds from them without detaching
+    (``dir_t`` (R): the assigned boxes' yaw, None without rotation; see demf_ca_head_loss_bwd)."""
+    return _CAHeadLoss.apply(cls_rows, reg_rows, ref_points, hyper12, distance_t, dir_class_t, dir_res_t, sem_t, obj_t,
+                             obj_w, box_w, dir_t)
+
+
 class _VoteLoss(Function):
     @staticmethod
     def forward(ctx, vote_points, seed_points, seed_indices, masks, vote_targets, gt_per_seed,
@@ -2048,6 +2109,36 @@ def detect_decode(layers, num_dir_bins, with_rot=True):
     box7, cosy, siny, obj, sem = f(B, K, 7), f(B, K), f(B, K), f(B, K), f(B, K, C)
     cls = torch.empty((B, K), dtype=torch.int64, device=dev)
     _ffi.call("demf_detect_decode", B, K, len(layers), C, int(num_dir_bins), int(bool(with_rot)), descs,
+              _p(box7), _p(cosy), _p(siny), _p(obj), _p(sem), _p(cls), _stream())
+    return box7, cosy, siny, obj, sem, cls
+
+
+def ca_detect_decode(reg_rows, cls_rows, ref_points, num_dir_bins, with_rot=True):
+    """Decode + score of ``CAVoteHead.get_bboxes`` in one launch (see demf_ca_detect_decode), straight from the raw
+    conv-head rows: reg_rows (B,K,6+2*num_dir_bins) = [log-distance 6 | dir class | dir residual], cls_rows
+    (B,K,2+C) = [objectness 2 | semantic C], ref_points (B,K,3); views with a unit last stride go in by pointer and
+    strides.  -> box7 (B,K,7), cos_yaw, sin_yaw, obj (B,K), sem (B,K,C), classes (B,K) int64: the outputs of
+    ``detect_decode``."""
+    B, K, nreg = reg_rows.shape
+    C = cls_rows.shape[2] - 2
+    if nreg != 6 + 2 * int(num_dir_bins) or C < 1:
+        raise ValueError(f"ca_detect_decode: reg rows of {nreg} / cls rows of {cls_rows.shape[2]} columns")
+    arrs, hold = [], []
+    for t, name, n in ((reg_rows, "reg_rows", nreg), (cls_rows, "cls_rows", C + 2), (ref_points, "ref_points", 3)):
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise RuntimeError(f"{name} must be a float32 GPU (HIP) tensor: demf_amd operators have no CPU path")
+        if tuple(t.shape) != (B, K, n):
+            raise ValueError(f"{name} must be {(B, K, n)}, got {tuple(t.shape)}")
+        if t.stride(-1) != 1 or min(t.stride(0), t.stride(1)) < 0 or (K > 1 and t.stride(1) < n) or \
+                max(t.stride(0), t.stride(1)) >= (1 << 31):
+            t = t.contiguous()
+        hold.append(t)
+        arrs += [t.data_ptr(), t.stride(0) if B > 1 else 0, max(t.stride(1), n)]
+    dev = reg_rows.device
+    f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)         # noqa: E731
+    box7, cosy, siny, obj, sem = f(B, K, 7), f(B, K), f(B, K), f(B, K), f(B, K, C)
+    cls = torch.empty((B, K), dtype=torch.int64, device=dev)
+    _ffi.call("demf_ca_detect_decode", B, K, C, int(num_dir_bins), int(bool(with_rot)), *arrs,
               _p(box7), _p(cosy), _p(siny), _p(obj), _p(sem), _p(cls), _stream())
     return box7, cosy, siny, obj, sem, cls
 

@@ -107,10 +107,13 @@ class ScenePipeline:
     """Per-scene host work (``load``) and the batched device work (``to_device``) of one pipeline mode."""
 
     def __init__(self, dataset, mode="train", img_scale=(1333, 800), num_points=20000, seed=0,
-                 img_norm=ops.IMG_NORM, pad_divisor=32):
+                 img_norm=ops.IMG_NORM, pad_divisor=32, with_img=True):
+        """``with_img=False`` (a points-only model): no image file is opened, nothing of it is uploaded and
+        ``image_prep`` is not launched; the batch has no ``img`` and its metas carry no image entries.  Points, random
+        draws and ground truth are those of the ``with_img=True`` pipeline for the same seed."""
         if mode not in ("train", "test"):
             raise ValueError(f"mode must be 'train' or 'test', got {mode!r}")
-        self.dataset, self.mode = dataset, mode
+        self.dataset, self.mode, self.with_img = dataset, mode, bool(with_img)
         self.img_scale, self.num_points, self.seed = tuple(img_scale), int(num_points), int(seed)
         self.img_norm, self.pad_divisor = img_norm, pad_divisor
 
@@ -127,16 +130,19 @@ class ScenePipeline:
     def _scene(self, index, epoch, info, img, source_meta, **source):
         """What ``load`` returns, from a decoded image and the point source's own entries: random draws, boxes and
         metadata."""
-        h, w = img.shape[:2]
         rng = self.scene_rng(index, epoch)
         params = draw_aug_params(rng) if self.mode == "train" else identity_aug_params()
         seed = int(rng.integers(0, 2 ** 63 - 1))
-        meta = dict(sample_idx=info["sample_idx"], **source_meta,
-                    img_filename=info["img_filename"], depth2img=info["depth2img"], flip=False,
-                    img_norm_cfg=dict(mean=np.asarray(self.img_norm[0], np.float32),
-                                      std=np.asarray(self.img_norm[1], np.float32), to_rgb=True))
-        meta = resize_meta(meta, (h, w), self.img_scale, self.pad_divisor)
-        meta["pad_shape"] = tuple(meta["batch_input_shape"]) + (3,)
+        if img is None:                             # with_img=False
+            meta = dict(sample_idx=info["sample_idx"], **source_meta, flip=False)
+        else:
+            h, w = img.shape[:2]
+            meta = dict(sample_idx=info["sample_idx"], **source_meta,
+                        img_filename=info["img_filename"], depth2img=info["depth2img"], flip=False,
+                        img_norm_cfg=dict(mean=np.asarray(self.img_norm[0], np.float32),
+                                          std=np.asarray(self.img_norm[1], np.float32), to_rgb=True))
+            meta = resize_meta(meta, (h, w), self.img_scale, self.pad_divisor)
+            meta["pad_shape"] = tuple(meta["batch_input_shape"]) + (3,)
         ann = info.get("ann_info")
         boxes = ann["gt_bboxes_3d"] if ann is not None else np.zeros((0, 7), np.float32)
         boxes, meta = apply_aug_params(boxes, meta, params)
@@ -149,7 +155,7 @@ class ScenePipeline:
         raw = np.fromfile(info["pts_filename"], dtype=np.float32)
         if raw.size == 0 or raw.size % LOAD_DIM:
             raise ValueError(f"{info['pts_filename']}: {raw.size} floats is not a positive multiple of {LOAD_DIM}")
-        return self._scene(index, epoch, info, self.read_image(info["img_filename"]),
+        return self._scene(index, epoch, info, self.read_image(info["img_filename"]) if self.with_img else None,
                            dict(pts_filename=info["pts_filename"]), raw=raw.reshape(-1, LOAD_DIM))
 
     # ---- the point source: what is uploaded for the clouds and how it becomes (raw, offsets) on the device ----------
@@ -172,6 +178,8 @@ class ScenePipeline:
         the current stream).  -> (batch dict, uploaded bytes).  The batch is valid on ``stream`` once the call
         returns; another stream must wait on it first."""
         B = len(scenes)
+        if not self.with_img:
+            return self._to_device_points(scenes, device, stream)
         nbytes = np.array([s["img"].size for s in scenes], np.int64)
         img_h = torch.empty((int(nbytes.sum()),), dtype=torch.uint8, pin_memory=True)
         img_np = img_h.numpy()
@@ -218,6 +226,40 @@ class ScenePipeline:
                                          for s in scenes]
         uploaded = sum(t.numel() * t.element_size() for t in big.values()) + img_h.numel() + small.numel() * 8
         return batch, uploaded
+
+    def _to_device_points(self, scenes, device, stream=None):
+        """``to_device`` without the image: the same point source, parameters, seeds and kernels (``points_floor``,
+        ``points_prep``) in the same order; no image bytes, offsets or shapes travel and ``image_prep`` is not launched."""
+        B = len(scenes)
+        big, words = self.pack_source(scenes)
+        words = dict(params=np.stack([param_row(s["params"]) for s in scenes]).reshape(-1), **words,
+                     seeds=np.array([s["seed"] for s in scenes], np.int64))
+        words = {k: np.ascontiguousarray(v).reshape(-1) for k, v in words.items()}
+        at, n = {}, 0
+        for k, v in words.items():
+            if v.nbytes % 8:
+                raise ValueError(f"{k}: {v.nbytes} bytes is not a whole number of 8-byte words")
+            at[k] = (n, n + v.nbytes // 8)
+            n += v.nbytes // 8
+        small = torch.empty((n,), dtype=torch.int64, pin_memory=True)
+        sm = small.numpy()
+        for k, v in words.items():
+            sm[at[k][0]:at[k][1]].view(v.dtype)[:] = v
+        stream = torch.cuda.current_stream(device) if stream is None else stream
+        with torch.cuda.stream(stream):
+            big_d = {k: t.to(device, non_blocking=True) for k, t in big.items()}
+            small_d = small.to(device, non_blocking=True)
+            sd = {k: small_d[a:b].view(getattr(torch, str(words[k].dtype))) for k, (a, b) in at.items()}
+            raw_d, poff_d = self.source_records(big_d, sd, None)
+            floor = ops.points_floor(raw_d, poff_d)
+            points = ops.points_prep(raw_d, poff_d, floor, sd["params"].view(B, 8), sd["seeds"], self.num_points)
+            batch = dict(points=points, img_metas=[dict(s["meta"]) for s in scenes])
+            if all(s["gt_labels_3d"] is not None for s in scenes):
+                batch["gt_bboxes_3d"] = [torch.from_numpy(np.ascontiguousarray(s["gt_bboxes_3d"])).to(device)
+                                         for s in scenes]
+                batch["gt_labels_3d"] = [torch.from_numpy(np.ascontiguousarray(s["gt_labels_3d"])).to(device)
+                                         for s in scenes]
+        return batch, sum(t.numel() * t.element_size() for t in big.values()) + small.numel() * 8
 
 
 class FramePipeline(ScenePipeline):
@@ -301,12 +343,15 @@ class SceneLoader:
     to its mode (``"train"`` otherwise)."""
 
     def __init__(self, dataset, batch_size, mode=None, seed=0, img_scale=(1333, 800), num_points=20000,
-                 workers=8, drop_last=False, device=None, pipeline=None):
+                 workers=8, drop_last=False, device=None, pipeline=None, with_img=None):
         if mode is None:
             mode = "train" if pipeline is None else pipeline.mode
         if pipeline is not None and pipeline.mode != mode:
             raise ValueError(f"the given pipeline is in {pipeline.mode!r} mode, the loader in {mode!r}")
-        self.pipeline = ScenePipeline(dataset, mode, img_scale, num_points, seed) if pipeline is None else pipeline
+        if pipeline is not None and with_img is not None and bool(with_img) != pipeline.with_img:
+            raise ValueError(f"the given pipeline was built with_img={pipeline.with_img}, the loader asks for {with_img}")
+        self.pipeline = ScenePipeline(dataset, mode, img_scale, num_points, seed,
+                                      with_img=True if with_img is None else with_img) if pipeline is None else pipeline
         self.dataset, self.batch_size, self.mode, self.seed = dataset, int(batch_size), mode, int(seed)
         self.drop_last = drop_last
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)

@@ -3,7 +3,7 @@
   python -m demf_amd.train --data-root R --ann-file sunrgbd_infos_train.pkl --work-dir W
                            [--val-ann-file sunrgbd_infos_val.pkl] [--load-from C] [--resume-from C] [--no-validate]
                            [--no-graphs] [--batch-size 16] [--epochs 36] [--seed 0] [--workers 4] [--log-interval 50]
-                           [--accumulate 1] [--autoscale-lr]
+                           [--accumulate 1] [--autoscale-lr] [--model {demf,votenet}]
 
 ``fit`` feeds a dataset through ``SceneLoader(mode="train")``, the frozen image stream and ``engine.Trainer`` (one
 captured hipGraph per batch shape, ``StepCache``).  Losses, gradient norm and learning rate are logged through the
@@ -203,6 +203,15 @@ class _Log:
         self.f.close()
 
 
+def model_loss_names(model):
+    """The scalars the step meter records for ``model``, in the order of its columns: the loss terms its head has
+    (``modules.VoteNet``'s CAVoteHead has no ``center_loss``), the vote loss and their sum."""
+    from .meter import loss_names
+    head = getattr(model, "bbox_head", None)
+    terms = getattr(head, "LOSS_NAMES", None)
+    return loss_names() if terms is None else tuple(terms) + ("vote_loss", "_total")
+
+
 def validate(model, val_set, batch_size, workers, num_points, img_scale, seed=0):
     """One validation pass: ``infer.run_test`` into a fresh store, ``val_set.evaluate``; the model goes back to
     ``train()`` (for ``DeMFVoteNet`` that keeps the image branch in eval)."""
@@ -223,8 +232,9 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
         eval_interval=DEFAULTS["eval_interval"], seed=DEFAULTS["seed"], workers=DEFAULTS["workers"], graphs=True,
         resume_from=None, load_from=None, num_points=20000, img_scale=(1333, 800), on_step=None, echo=True,
         val_batch_size=None, accumulate=DEFAULTS["accumulate"]):
-    """Train ``model`` (a ``DeMFVoteNet``: frozen image stream + hot path) on ``train_set`` for ``max_epochs`` runner
-    epochs of ``repeat`` passes each.  -> dict(trainer, meter, stepper, epoch, iter, val).
+    """Train ``model`` (a ``DeMFVoteNet``: frozen image stream + hot path; or a model without ``extract_img_feat``,
+    ``modules.VoteNet``: from points alone - the loader then reads, decodes and uploads no image) on ``train_set`` for
+    ``max_epochs`` runner epochs of ``repeat`` passes each.  -> dict(trainer, meter, stepper, epoch, iter, val).
 
     ``on_step(info)``: called after every micro-step has been enqueued, ``info = dict(epoch, iter, indices, loss,
     micro)`` with the 1-based epoch and global iteration, the batch's dataset indices, the batch's loss as a DEVICE
@@ -236,15 +246,14 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
     (``accumulation_plan``; the epoch's last log line carries ``discarded``), so that checkpoints, learning-rate
     changes and validation fall on step boundaries."""
     from . import engine, infer
-    from .meter import StepMeter, loss_names
+    from .meter import StepMeter
     from .modules import DeMFHotPath
     from .pipeline import SceneLoader
     if batch_size < 1 or max_epochs < 0 or repeat < 1 or log_interval < 1 or ckpt_interval < 1 or eval_interval < 1:
         raise ValueError("batch_size, repeat, log_interval, ckpt_interval and eval_interval must be positive")
     if isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1:
         raise ValueError("accumulate must be a positive integer, got %r" % (accumulate,))
-    if not hasattr(model, "extract_img_feat"):
-        raise TypeError("fit() trains a detector with an image stream (DeMFVoteNet): the loader yields images")
+    with_img = hasattr(model, "extract_img_feat")
     os.makedirs(work_dir, exist_ok=True)
     torch.manual_seed(seed)                       # (the Trainer seeds the dropout counter from it)
     model.cuda().train()
@@ -257,8 +266,9 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
                   flush=True)
     # the runner computes the frozen image features itself and drives the hot path's forward_train
     trainer = engine.Trainer(model, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
-                             forward=functools.partial(DeMFHotPath.forward_train, model), accumulate=accumulate)
-    names = loss_names()
+                             forward=functools.partial(DeMFHotPath.forward_train, model) if with_img else None,
+                             accumulate=accumulate)
+    names = model_loss_names(model)
     meter = StepMeter(names, ring_rows=max(128, 2 * log_interval))
     trainer.attach_meter(meter)
     epoch0, it = 0, 0
@@ -269,7 +279,7 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
         epoch0, it = int(meta["epoch"]), int(meta["iter"])
     stepper = trainer.bucketed() if graphs else None
     loader = SceneLoader(train_set, batch_size, "train", seed=seed, img_scale=img_scale, num_points=num_points,
-                         workers=workers)
+                         workers=workers, with_img=with_img)
     ipe, dropped = accumulation_plan(len(loader), repeat, accumulate)      # iterations per runner epoch
     log = _Log(os.path.join(work_dir, "train.log.json"), echo)
     rows, marks = [], []                          # meter rows not logged yet; (last t, epoch, iter, s/iter) per interval
@@ -303,9 +313,11 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
             for rep in range(repeat):
                 loader.epoch = loader_epoch(epoch, rep, repeat)
                 for batch, nxt in _lookahead(loader):
-                    feats = model.extract_img_feat(batch["img"], batch["img_metas"])
-                    step_batch = dict(points=batch["points"], img_features=feats, img_metas=batch["img_metas"],
-                                      gt_bboxes_3d=batch["gt_bboxes_3d"], gt_labels_3d=batch["gt_labels_3d"])
+                    step_batch = dict(points=batch["points"], gt_bboxes_3d=batch["gt_bboxes_3d"],
+                                      gt_labels_3d=batch["gt_labels_3d"])
+                    if with_img:
+                        step_batch.update(img_features=model.extract_img_feat(batch["img"], batch["img_metas"]),
+                                          img_metas=batch["img_metas"])
                     micro = trainer.micro
                     if stepper is not None:
                         loss = stepper.step(step_batch, next_points=None if nxt is None else nxt["points"])
@@ -361,6 +373,9 @@ def parse_args(argv=None):
                    help="batches per optimizer step (8: the reference's 8-GPU step on one GPU)")
     p.add_argument("--autoscale-lr", action="store_true",
                    help="the reference's linear scaling rule: lr x accumulate / 8")
+    p.add_argument("--model", choices=("demf", "votenet"), default="demf",
+                   help="demf: DeMFVoteNet (configs/demf/demf_votenet.py); votenet: the points-only class-agnostic "
+                        "baseline (configs/baseline/votenet.py), trained without reading an image")
     args = p.parse_args(argv)
     if args.batch_size < 1 or args.workers < 1 or args.log_interval < 1 or args.accumulate < 1:
         p.error("--batch-size, --workers, --log-interval and --accumulate must be positive")
@@ -381,8 +396,8 @@ def main(argv=None, model=None, **fit_kwargs):
     if args.val_ann_file and not args.no_validate:
         val_set = SUNRGBDDataset(args.data_root, args.val_ann_file, test_mode=True)
     if model is None:
-        from .modules import DeMFVoteNet
-        model = DeMFVoteNet()
+        from .modules import DeMFVoteNet, VoteNet
+        model = VoteNet() if args.model == "votenet" else DeMFVoteNet()
     kw = dict(val_set=val_set, batch_size=args.batch_size, max_epochs=args.epochs, seed=args.seed,
               workers=args.workers, log_interval=args.log_interval, graphs=not args.no_graphs,
               resume_from=args.resume_from, load_from=args.load_from, accumulate=args.accumulate)

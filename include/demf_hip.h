@@ -619,6 +619,34 @@ DEMF_INTERNAL int demf_head_loss_bwd(int R, int num_dir_bins, int num_classes, c
                        float* grad_cls, float* grad_reg, float* grad_base,
                        demf_stream_t stream);
 
+/* The distance form of the same: CAVoteHead.loss (class_agnostic_vote_head.py:40-121) of the points-only
+ * class-agnostic VoteNet baseline (configs/baseline/votenet.py), with ClassAgnosticBBoxCoder.split_pred
+ * (class_agnostic_bbox_coder.py:88-127) folded in.  reg (R,30) = [log-distance to the six box faces 6 |
+ * dir class 12 | dir residual 12]; distance = exp(reg[0:6]).  distance_t (R,6) as demf_proposal_targets
+ * writes it (unclamped; clamped at 0 here, class_agnostic_vote_head.py:301).  Terms: objectness CE,
+ * SmoothL1 of the six distances (beta = hyper12[10], weight hyper12[5]), direction class / residual and
+ * semantic CE as above, AxisAlignedIoULoss on the corners (ref - d[3:6], ref + d[0:3]) against those of the
+ * targets - a function of the distances alone, so no reference point is read.
+ * There is no centre term: hyper12[6] and hyper12[11] are ignored and out7[4] receives exact zeros, so the
+ * seven-slot layout (and demf_loss_total / demf_scalars_accum / demf_step_meter behind it) is shared.     */
+DEMF_INTERNAL int demf_ca_head_loss_fwd(int R, int num_dir_bins, int num_classes, const float* hyper12,
+                       const float* cls, const float* reg, const float* distance_t,
+                       const int64_t* dir_class_t, const float* dir_res_t, const int64_t* sem_t,
+                       const int64_t* obj_t, const float* obj_w, const float* box_w, float* out7,
+                       demf_stream_t stream);
+/* gradients wrt cls (R,12) and reg (R,30) given the seven upstream scalars grad_out7 (device).
+ * grad_ref (R,3), nullable: the gradient wrt the reference points.  The reference builds distance_t from the
+ * proposal point without detaching it (class_agnostic_vote_head.py:271-294, clamp_ at :301), so the SmoothL1
+ * and IoU terms reach the point through their TARGETS: d t[0:3] = -Rz(-yaw) d point, d t[3:6] = +Rz(-yaw) d point
+ * where the unclamped target is >= 0.  dir_t (R), nullable = the assigned boxes' yaw (dir_targets of
+ * demf_proposal_targets; NULL: no rotation).                                                             */
+DEMF_INTERNAL int demf_ca_head_loss_bwd(int R, int num_dir_bins, int num_classes, const float* hyper12,
+                       const float* cls, const float* reg, const float* distance_t,
+                       const int64_t* dir_class_t, const float* dir_res_t, const int64_t* sem_t,
+                       const int64_t* obj_t, const float* obj_w, const float* box_w,
+                       const float* grad_out7, const float* dir_t, float* grad_cls, float* grad_reg,
+                       float* grad_ref, demf_stream_t stream);
+
 /* VoteModule.get_loss (called at class_agnostic_vote_head.py:641-644): chamfer-L1 of each
  * seed's vote against its gt_per_seed target votes, min over targets, weighted by
  * mask/(mask_sum+1e-6)*dst_weight.  grad_out == NULL: forward (out accumulated);
@@ -821,6 +849,18 @@ typedef struct demf_detect_layer {
 DEMF_INTERNAL int demf_detect_decode(int B, int K, int L, int C, int num_dir_bins, int with_rot,
                        const demf_detect_layer* layers, float* box7, float* cos_yaw, float* sin_yaw,
                        float* obj, float* sem, int64_t* classes, demf_stream_t stream);
+
+/* The distance form of the same for the one layer of CAVoteHead: ClassAgnosticBBoxCoder.decode
+ * (class_agnostic_bbox_coder.py:42-86) + the scoring of mmdet3d VoteHead.get_bboxes, straight from the raw
+ * conv-head rows reg (B,K,6+2*num_dir_bins) / cls (B,K,2+C) and the reference points ref (B,K,3), each given
+ * by pointer, batch stride (_sb) and row stride (_sk) in floats, unit last stride.  d = exp(reg[0:6]);
+ * yaw = class2angle(argmax dir_class, dir_res_norm[argmax] * pi / num_dir_bins) mod 2pi (0 without rotation);
+ * size = max(d[0:3] + d[3:6], 0.1); centre = ref - Rz(yaw) . (d[3:6] - d[0:3]) / 2 with mmdet3d's
+ * rotation_3d_in_axis(axis=2) convention (x c + y s, -x s + y c).  Outputs as demf_detect_decode.        */
+DEMF_INTERNAL int demf_ca_detect_decode(int B, int K, int C, int num_dir_bins, int with_rot,
+                       const float* reg, int reg_sb, int reg_sk, const float* cls, int cls_sb, int cls_sk,
+                       const float* ref, int ref_sb, int ref_sk, float* box7, float* cos_yaw,
+                       float* sin_yaw, float* obj, float* sem, int64_t* classes, demf_stream_t stream);
 
 /* Selection of get_bboxes (class_agnostic_vote_head.py:735-754; mmdet3d multiclass_nms_single's
  * per_class_proposal branch) into a detection store: survivors = keep & (obj > score_thr).  Scene b of the batch
