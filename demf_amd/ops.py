@@ -6,6 +6,7 @@ reference calls (cited per function); tensors stay PyTorch-ROCm tensors and only
 raw device pointers + the current HIP stream cross the C ABI.  There is no CPU or
 eager fallback: a CPU tensor or a missing library raises.
 """
+import collections
 import ctypes
 
 import torch
@@ -1060,12 +1061,16 @@ _NO_BF16_STORE = not switches.env_int("DEMF_BF16_STORE")
 _VEC_FIN = switches.env_int("DEMF_VEC_FIN")   # A/B: bit 0 sparse reduce, 1 fused, 2 dx_red
 
 
+def _bwd_fuse_on(ns, sparse):
+    """What every one-pass backward needs: the switch, a bf16 / split-term compute mode, and - for the pooled
+    (sparse) gradient - groups of a multiple of 4 rows."""
+    return not (_NO_BWD_FUSE or _COMPUTE_MODE not in (1, 2) or (sparse and (ns < 4 or ns % 4)))
+
+
 def _bwd_fused_ok(N, K, ns, sparse, first=False):
     """Shapes / modes demf_mlp_bwd_fused covers (csrc/mlp_bwd.hip): one pass over a layer's saved
     output for dX, dW and the sums of the layer below, instead of a dx and a dW launch."""
-    if _NO_BWD_FUSE or _COMPUTE_MODE not in (1, 2):
-        return False
-    if sparse and (ns < 4 or ns % 4):
+    if not _bwd_fuse_on(ns, sparse):
         return False
     if first:
         return N == 64 and K == 64 and not sparse
@@ -1080,11 +1085,8 @@ def _bwd_fused_cols_ok(R, N, K, ns, sparse):
     """demf_mlp_bwd_fused_cols: the one-pass backward on 128-column chunks of a 256-output layer whose
     input has K = 256 / 384 / 512 channels (the vote aggregation stack), on enough rows to fill the
     persistent grid."""
-    if _NO_BWD_FUSE or _COMPUTE_MODE not in (1, 2) or _FUSED_COLS_MIN_R <= 0 or R < _FUSED_COLS_MIN_R:
-        return False
-    if sparse and (ns < 4 or ns % 4):
-        return False
-    return N == 256 and K > 128 and K % 128 == 0 and K <= 512
+    return (_bwd_fuse_on(ns, sparse) and 0 < _FUSED_COLS_MIN_R <= R
+            and N == 256 and K > 128 and K % 128 == 0 and K <= 512)
 
 
 # rows from which such a layer takes the one-pass backward as ONE launch over all its 128-column chunks
@@ -1095,11 +1097,7 @@ _FUSED_WIDE_MIN_R = switches.env_int("DEMF_FUSED_WIDE_MIN_R")
 def _bwd_fused_wide_ok(R, N, K, ns, sparse):
     """demf_mlp_bwd_fused_wide: a 256-output layer whose input has K = 256 / 384 / 512 channels (the vote
     aggregation's layers 2 and 3), on enough rows to fill the persistent grid."""
-    if _NO_BWD_FUSE or _COMPUTE_MODE not in (1, 2) or _FUSED_WIDE_MIN_R <= 0 or R < _FUSED_WIDE_MIN_R:
-        return False
-    if sparse and (ns < 4 or ns % 4):
-        return False
-    return N == 256 and K in (256, 384, 512)
+    return _bwd_fuse_on(ns, sparse) and 0 < _FUSED_WIDE_MIN_R <= R and N == 256 and K in (256, 384, 512)
 
 
 # SA1's pooled last layer without its (R x 128) output: the forward does not store it, the backward is
@@ -1160,20 +1158,109 @@ def reset_accumulators():
         buf.zero_()
 
 
+# One layer of a stack, as shared_mlp_pool flattens it for Function.apply (7 tensors per layer, in this order).
+_Layer = collections.namedtuple("_Layer", "W gamma beta rmean rvar bias nbt")
+# What the forward decided (_fwd_plan), kept on ctx: the compute mode it ran in, and per layer the form's name.
+_FwdPlan = collections.namedtuple("_FwdPlan", "mode store16 noy x4 fuse_pool fwd")
+# A layer's backward (_bwd_form).  variant: two_launch's input-gradient launch (None: no input gradient), or "x4" for
+# a fused_first whose layer 0 output was never stored; first_tail: two_launch's demf_mlp_gemm_bwd_dx_first ends layer 0.
+_BwdForm = collections.namedtuple("_BwdForm", "form variant first_tail", defaults=(None, False))
+
+
+def _fwd_plan(R, ld, ns, shapes, training, has_geo, x_requires_grad):
+    """Every form decision of the forward, from sizes and flags alone (shapes: (N, K) per layer; R: the rows the GEMMs
+    see; ld: the width of x); reads the compute mode and the switches when called.  Forms, entry points and
+    conditions in words: DESIGN.md section 3.2."""
+    L, shapes = len(shapes), [tuple(s) for s in shapes]
+    pool = training and not _NO_FUSED_POOL and ns in (16, 32, 64)
+    # bf16 compute mode (BASELINE configs[3]): SA1-shaped stacks (4-float rows -> 64 -> 64 -> 128, the
+    # 1 M-row layers that carry most of the step's HBM traffic) keep the raw outputs of layers 1 and 2
+    # - and the gradient that flows between their backwards - as bf16 rows; every kernel on that path
+    # is a round-3 kernel that loads / stores them directly (csrc/mlp.hip mlp_fwd_res_kernel,
+    # csrc/mlp_bwd.hip).  Statistics, pooled extrema, vectors and weight gradients stay fp32.
+    store16 = (_COMPUTE_MODE == 1 and not _NO_BF16_STORE and pool and not has_geo and L == 3
+               and ld == 4 and not x_requires_grad and R >= 16384 and R % 64 == 0
+               and not _NO_BWD_FUSE and not _NO_FIRST_FUSE and shapes == [(64, 4), (64, 64), (128, 64)])
+    noy = not has_geo and not store16 and L >= 2 and ld % 4 == 0 and _pool_noy_ok(R, ns, shapes, training, pool)
+    x4 = not has_geo and not store16 and _sa1_x4_ok(R, ld, shapes, training, x_requires_grad, ns)
+    fuse_pool = pool and L > 1            # last layer: the max over the ns neighbours rides in the GEMM epilogue
+    fwd = []
+    for l in range(L):
+        if has_geo and l == 0:
+            fwd.append("group_first")
+        elif fuse_pool and l == L - 1:
+            fwd.append("pool_noy" if noy else "pool_st16" if store16 else "pool")
+        elif not training:
+            fwd.append("eval")
+        elif x4 and l < 2:
+            fwd.append(("first_stats", "bn_x4")[l])
+        else:
+            fwd.append("bn_st16" if store16 and l == 1 else "bn")
+    return _FwdPlan(_COMPUTE_MODE, bool(store16), bool(noy), bool(x4), bool(fuse_pool), tuple(fwd))
+
+
+def _bwd_form(plan, l, L, N, K, ldx, ns, R, sparse, fuse_first, needs_x_grad, has_geo):
+    """The backward of layer l (weight (N, K), input rows ldx wide; sparse: its gradient is still the pooled one), in
+    the order of precedence.  Forms, entry points and conditions in words: DESIGN.md section 3.2."""
+    if l == 0 and has_geo:
+        return _BwdForm("geo_first")
+    first_here = l == 1 and fuse_first
+    if l == L - 1 and plan.noy:
+        return _BwdForm("pool_noy")
+    if l > 0 and ldx == K:
+        if _bwd_fused_ok(N, K, ns, sparse, first_here):
+            return _BwdForm("fused_first", "x4" if plan.x4 else None) if first_here else _BwdForm("fused")
+        if not first_here and not plan.store16 and _bwd_fused_cols_ok(R, N, K, ns, sparse):
+            return _BwdForm("fused_cols")
+        if not first_here and not plan.store16 and _bwd_fused_wide_ok(R, N, K, ns, sparse):
+            return _BwdForm("fused_wide")
+    if first_here:
+        return _BwdForm("two_launch", None, True)
+    if l == 0 and not needs_x_grad:
+        return _BwdForm("two_launch")
+    if K % 4 == 0 and l > 0 and not _NO_RED_FUSE:
+        # + layer l-1's BN-backward sums from the output tiles (no separate reduce pass); _v: + its vectors
+        return _BwdForm("two_launch", "dx_red_v" if _VEC_FIN & 4 else "dx_red")
+    return _BwdForm("two_launch", "dx_w" if K % 4 == 0 else "dx")
+
+
+
+def _bwd_forms(plan, R, ld, ns, shapes, needs_x_grad, has_geo):
+    """fuse_first and {l: _bwd_form} of the layers the backward visits, last layer first: it ends with geo_first,
+    fused_first or a first_tail, each of which finishes layer 0 as well.
+    fuse_first - SA1-like stacks (4-float input rows, no input gradient, >= 3 layers): layer 0's backward is
+    taken from the output tile of layer 1's dx GEMM, whose (R x N0) result is never stored."""
+    L, N0 = len(shapes), shapes[0][0]
+    fuse_first = (not has_geo and L >= 3 and not needs_x_grad and ld == 4 and N0 <= 64 and N0 % 4 == 0
+                  and not _NO_FIRST_FUSE)
+    forms = {}
+    for l in range(L - 1, -1, -1):
+        N, K = shapes[l]
+        f = forms[l] = _bwd_form(plan, l, L, N, K, shapes[l - 1][0] if l else ld, ns, R, l == L - 1, fuse_first,
+                                 needs_x_grad, has_geo)
+        if f.form in ("geo_first", "fused_first") or f.first_tail:
+            break
+    return fuse_first, forms
+
+
 class _SharedMLPPool(Function):
     """x (R, ld) rows -> pooled (R/ns, C_L).  Per layer l the tensors are
-    (W_l (N_l, K_l), gamma_l, beta_l, running_mean_l, running_var_l, conv_bias_l|None);
+    (W_l (N_l, K_l), gamma_l, beta_l, running_mean_l, running_var_l, conv_bias_l|None, num_batches_tracked_l|None);
     K_0 == ld.  A conv bias in front of a train-mode BN cancels in the output, so it never
     reaches the kernels; its gradient is returned as exact zeros.
     Forward never materialises a BN/ReLU output: only the raw conv outputs Y_l are stored
     (needed for backward), statistics come out of the GEMM epilogue, and the last
-    BN+ReLU is fused with the max over the ``ns`` neighbours (ns == 1: plain activation)."""
+    BN+ReLU is fused with the max over the ``ns`` neighbours (ns == 1: plain activation).
+    Which kernel a layer takes is decided by _fwd_plan and _bwd_form alone; the launches below dispatch on them."""
 
     @staticmethod
     def forward(ctx, x, ns, training, eps, momentum, geo, geo_xyz, geo_center, *tensors):
         _chk(x, "x")
         R, ld = x.shape
         L = len(tensors) // 7
+        assert len(tensors) == 7 * L
+        layers = [_Layer(*tensors[7 * l:7 * l + 7]) for l in range(L)]
+        shapes = [tuple(_chk(lay.W, "weight").shape) for lay in layers]
         if geo is not None:
             # x = per-point feature rows (B*N, C); the grouped rows never exist (csrc/group_first.hip)
             g_xyz, g_center, g_idx, g_off, g_rows, g_radius, g_norm = geo
@@ -1182,164 +1269,96 @@ class _SharedMLPPool(Function):
             _chk(g_idx, "idx", torch.int32)
             gB, gN, _ = g_xyz.shape
             _, gM, gns = g_idx.shape
-            assert gns == ns and R == gB * gN and L >= 2 and tensors[0].shape[1] == ld + 3
+            assert gns == ns and R == gB * gN and L >= 2 and shapes[0][1] == ld + 3
             R = gB * gM * ns
-        assert len(tensors) == 7 * L and R % ns == 0
+        assert R % ns == 0
         dev = x.device
         st = _stream()
+        plan = _fwd_plan(R, ld, ns, shapes, training, geo is not None, x.requires_grad)
         Ys, sss, mis = [], [], []
         cur, cur_ld, pro = x, ld, None
-        fuse_pool = False
-        # bf16 compute mode (BASELINE configs[3]): SA1-shaped stacks (4-float rows -> 64 -> 64 -> 128, the
-        # 1 M-row layers that carry most of the step's HBM traffic) keep the raw outputs of layers 1 and 2
-        # - and the gradient that flows between their backwards - as bf16 rows; every kernel on that path
-        # is a round-3 kernel that loads / stores them directly (csrc/mlp.hip mlp_fwd_res_kernel,
-        # csrc/mlp_bwd.hip).  Statistics, pooled extrema, vectors and weight gradients stay fp32.
-        store16 = (_COMPUTE_MODE == 1 and not _NO_BF16_STORE and training and geo is None and L == 3
-                   and ld == 4 and not x.requires_grad and R >= 16384 and R % 64 == 0
-                   and ns in (16, 32, 64) and not _NO_FUSED_POOL and not _NO_BWD_FUSE and not _NO_FIRST_FUSE
-                   and [tuple(tensors[7 * l].shape) for l in range(3)] == [(64, 4), (64, 64), (128, 64)])
-        noy = geo is None and not store16 and L >= 2 and ld % 4 == 0 and _pool_noy_ok(
-            R, ns, [tuple(tensors[7 * l].shape) for l in range(L)], training,
-            training and not _NO_FUSED_POOL and ns in (16, 32, 64))
-        x4 = geo is None and not store16 and _sa1_x4_ok(
-            R, ld, [tuple(tensors[7 * l].shape) for l in range(L)], training, x.requires_grad, ns)
         # the self-cleaning fp64 accumulator holds every layer's statistics (no fill launches)
-        ws = _accum64(2 * sum(tensors[7 * l].shape[0] for l in range(L)), dev) if training else None
-        woff = 0
-        for l in range(L):
-            W, gamma, beta, rmean, rvar = tensors[7 * l:7 * l + 5]
-            nbt = tensors[7 * l + 6]
-            _chk(W, "weight")
-            N, K = W.shape
-            first_geo = geo is not None and l == 0
-            assert first_geo or K == cur_ld, \
+        n_stats = 2 * sum(N for N, _ in shapes)
+        ws = _Bump(_accum64(n_stats, dev)[:n_stats]) if training else None
+        for l, (lay, form) in enumerate(zip(layers, plan.fwd)):
+            W, (N, K) = lay.W, shapes[l]
+            assert form == "group_first" or K == cur_ld, \
                 f"layer {l}: weight has {K} input columns, rows have {cur_ld}"
-            # (x4: layer 0's output is never written - an empty placeholder keeps the saved-tensor layout)
-            Y = torch.empty((0 if (x4 and l == 0) else R, N),
-                            dtype=torch.bfloat16 if (store16 and l >= 1) else torch.float32, device=dev)
+            # (first_stats, pool_noy: the output is never written - an empty placeholder keeps the saved-tensor layout)
+            Y = torch.empty((0 if form in ("first_stats", "pool_noy") else R, N), device=dev,
+                            dtype=torch.bfloat16 if form in ("bn_st16", "pool_st16") else torch.float32)
             ss = torch.empty(2 * N, dtype=torch.float32, device=dev)
             mi = torch.empty(2 * N, dtype=torch.float32, device=dev)
-            fuse_pool = training and l == L - 1 and l > 0 and not _NO_FUSED_POOL and \
-                ns in (16, 32, 64)
-            if first_geo:
+            stats = ws.take(2 * N) if training else None
+            # (train mode: + the BatchNorm bookkeeping, by the launch's last workgroup)
+            tail = _bn_tail(lay, eps, momentum, ss, mi) if training else _BN_TAIL_EVAL
+            gemm = (R, K, N, cur_ld, _p(cur), _p(pro), _p(W))
+            if form == "group_first":
                 # reference column order [xyz(3) | feat(C)]: U = feat . Wf^T once per source point
                 U = torch.empty((x.shape[0], N), dtype=torch.float32, device=dev)
                 from . import fused
                 fused.gemm(x.shape[0], N, ld, _p(x), (ld, 1), W.data_ptr() + 12, (K, 1), _p(U), N)
                 ctx.geo_U = U if training else None     # the backward forms y again from it instead of reading Y_0
-                stats = None
-                if training:
-                    stats = ws[woff:woff + 2 * N]
-                    woff += 2 * N
                 # (the xyz columns of W are read in place: w_ld = K)
-                # (train mode: + the BatchNorm bookkeeping, by the launch's last workgroup)
-                fin = (_p(gamma), _p(beta), float(eps), float(momentum), _p(rmean), _p(rvar), _p(nbt), _p(ss), _p(mi),
-                       _p(tensors[7 * l + 5])) if training else (None, None, 0.0, 0.0, None, None, None, None, None, None)
-                _ffi.call("demf_group_first_fwd", gB, gN, gM, ns, N, float(g_radius),
-                          int(bool(g_norm)), _p(g_xyz), _p(g_center), _p(g_idx), _p(U), _p(W), K,
-                          _p(Y), _p(stats), *fin, st)
-                if not training:
-                    invstd = torch.rsqrt(rvar + eps)
-                    ss[:N] = gamma * invstd
-                    ss[N:] = beta - rmean * gamma * invstd
-                    mi[:N] = rmean
-                    mi[N:] = invstd
-            elif fuse_pool:
-                # last layer: the max over the ns neighbours rides in the GEMM epilogue
-                stats = ws[woff:woff + 2 * N]
-                woff += 2 * N
+                _ffi.call("demf_group_first_fwd", gB, gN, gM, ns, N, float(g_radius), int(bool(g_norm)), _p(g_xyz),
+                          _p(g_center), _p(g_idx), _p(U), _p(W), K, _p(Y), _p(stats), *tail, st)
+            elif form in ("pool", "pool_noy", "pool_st16"):
                 # only the extremum the sign of gamma selects (pmin / amin = NULL)
                 pm = torch.empty((R // ns, N), dtype=torch.float32, device=dev)
                 am = torch.empty((R // ns, N), dtype=torch.int32, device=dev)
-                # (+ the BN bookkeeping, in the GEMM's last workgroup)
-                if noy:
-                    # the raw (R x N) output is never written: its backward needs the layer's INPUT only
-                    Y = torch.empty((0, N), dtype=torch.float32, device=dev)
-                    _ffi.call("demf_mlp_gemm_fwd_pool_bn_st", R, K, N, cur_ld, _p(cur), _p(pro), _p(W), None,
-                              _p(stats), ns, _p(pm), _p(am), _p(gamma), _p(beta), float(eps),
-                              float(momentum), _p(rmean), _p(rvar), _p(nbt), _p(ss), _p(mi),
-                              _p(tensors[7 * l + 5]), 4, st)
-                elif store16:
-                    _ffi.call("demf_mlp_gemm_fwd_pool_bn_st", R, K, N, cur_ld, _p(cur), _p(pro), _p(W), _p(Y),
-                              _p(stats), ns, _p(pm), _p(am), _p(gamma), _p(beta), float(eps),
-                              float(momentum), _p(rmean), _p(rvar), _p(nbt), _p(ss), _p(mi),
-                              _p(tensors[7 * l + 5]), 3, st)
+                if form == "pool":
+                    _ffi.call("demf_mlp_gemm_fwd_pool_bn", *gemm, _p(Y), _p(stats), ns, _p(pm), None, _p(am), None,
+                              *tail, st)
                 else:
-                    _ffi.call("demf_mlp_gemm_fwd_pool_bn", R, K, N, cur_ld, _p(cur), _p(pro), _p(W), _p(Y),
-                              _p(stats), ns, _p(pm), None, _p(am), None, _p(gamma),
-                              _p(beta), float(eps), float(momentum), _p(rmean), _p(rvar), _p(nbt), _p(ss),
-                              _p(mi), _p(tensors[7 * l + 5]), st)
-            elif training and x4 and l == 0:
+                    # (pool_noy: the raw output is never written - its backward needs the layer's INPUT only)
+                    _ffi.call("demf_mlp_gemm_fwd_pool_bn_st", *gemm, None if form == "pool_noy" else _p(Y), _p(stats),
+                              ns, _p(pm), _p(am), *tail, 4 if form == "pool_noy" else 3, st)
+            elif form == "first_stats":
                 # statistics of y = x.W0^T from the second moments of the 16-byte rows; no output
-                stats = ws[woff:woff + 2 * N]
-                woff += 2 * N
-                _ffi.call("demf_mlp_first_stats", R, N, _p(cur), _p(W), _p(stats), _p(gamma), _p(beta), float(eps),
-                          float(momentum), _p(rmean), _p(rvar), _p(nbt), _p(ss), _p(mi), _p(tensors[7 * l + 5]), st)
-            elif training and x4 and l == 1:
-                stats = ws[woff:woff + 2 * N]
-                woff += 2 * N
-                _ffi.call("demf_mlp_gemm_fwd_bn_x4", R, N, _p(x), _p(tensors[0]), _p(pro), _p(W), _p(Y), _p(stats),
-                          _p(gamma), _p(beta), float(eps), float(momentum), _p(rmean), _p(rvar), _p(nbt),
-                          _p(ss), _p(mi), _p(tensors[7 * l + 5]), st)
-            elif training:
-                stats = ws[woff:woff + 2 * N]
-                woff += 2 * N
-                if store16 and l == 1:
-                    _ffi.call("demf_mlp_gemm_fwd_bn_st", R, K, N, cur_ld, _p(cur), _p(pro), _p(W), _p(Y),
-                              _p(stats), _p(gamma), _p(beta), float(eps), float(momentum), _p(rmean),
-                              _p(rvar), _p(nbt), _p(ss), _p(mi), _p(tensors[7 * l + 5]), 2, st)
-                else:
-                    _ffi.call("demf_mlp_gemm_fwd_bn", R, K, N, cur_ld, _p(cur), _p(pro), _p(W), _p(Y),
-                              _p(stats), _p(gamma), _p(beta), float(eps), float(momentum), _p(rmean),
-                              _p(rvar), _p(nbt), _p(ss), _p(mi), _p(tensors[7 * l + 5]), st)
+                _ffi.call("demf_mlp_first_stats", R, N, _p(cur), _p(W), _p(stats), *tail, st)
+            elif form == "bn_x4":
+                _ffi.call("demf_mlp_gemm_fwd_bn_x4", R, N, _p(x), _p(layers[0].W), _p(pro), _p(W), _p(Y), _p(stats),
+                          *tail, st)
+            elif form == "bn_st16":
+                _ffi.call("demf_mlp_gemm_fwd_bn_st", *gemm, _p(Y), _p(stats), *tail, 2, st)
+            elif form == "bn":
+                _ffi.call("demf_mlp_gemm_fwd_bn", *gemm, _p(Y), _p(stats), *tail, st)
             else:
-                _ffi.call("demf_mlp_gemm_fwd", R, K, N, cur_ld, _p(cur), _p(pro), _p(W), _p(Y),
-                          None, st)
-                invstd = torch.rsqrt(rvar + eps)
-                ss[:N] = gamma * invstd
-                ss[N:] = beta - rmean * gamma * invstd
-                mi[:N] = rmean
-                mi[N:] = invstd
+                assert form == "eval"
+                _ffi.call("demf_mlp_gemm_fwd", *gemm, _p(Y), None, st)
+            if not training:
+                _eval_scale_shift(lay, eps, ss, mi)
             Ys.append(Y)
             sss.append(ss)
             mis.append(mi)
             cur, cur_ld, pro = Y, N, ss
-        C = Ys[-1].shape[1]
+        C = shapes[-1][0]
         out = torch.empty((R // ns, C), dtype=torch.float32, device=dev)
         arg = torch.empty((R // ns, C), dtype=torch.int32, device=dev)
         yraw = None
-        if fuse_pool:
+        if plan.fuse_pool:
             # + the raw output at the selected rows: the sparse BN-backward reduce reads it
             # instead of gathering 2 M scattered values from the (R x C) output
             yraw = torch.empty((R // ns, C), dtype=torch.float32, device=dev)
-            if noy:
+            if plan.noy:
                 _ffi.call("demf_pool_select_slot0", R // ns, C, _p(pm), _p(am), _p(sss[-1]), _p(out), _p(arg),
                           _p(yraw), st)
             else:
-                _ffi.call("demf_pool_select", R // ns, C, _p(pm), _p(pm), _p(am), _p(am),
-                          _p(sss[-1]), _p(out), _p(arg), _p(yraw), st)
+                _ffi.call("demf_pool_select", R // ns, C, _p(pm), _p(pm), _p(am), _p(am), _p(sss[-1]), _p(out), _p(arg),
+                          _p(yraw), st)
         else:
-            _ffi.call("demf_bnrelu_maxpool_fwd", R // ns, ns, C, _p(Ys[-1]), _p(sss[-1]), _p(out),
-                      _p(arg), st)
-        ctx.save_for_backward(x, arg, *Ys, *sss, *mis, *[tensors[7 * l] for l in range(L)],
-                              *[tensors[7 * l + 1] for l in range(L)],
-                              *([yraw] if yraw is not None else []))
-        ctx.bias_shapes = [None if tensors[7 * l + 5] is None else tensors[7 * l + 5].shape
-                           for l in range(L)]
+            _ffi.call("demf_bnrelu_maxpool_fwd", R // ns, ns, C, _p(Ys[-1]), _p(sss[-1]), _p(out), _p(arg), st)
+        ctx.save_for_backward(x, arg, *Ys, *sss, *mis, *[lay.W for lay in layers],
+                              *[lay.gamma for lay in layers], *([yraw] if yraw is not None else []))
+        ctx.bias_shapes = [None if lay.bias is None else lay.bias.shape for lay in layers]
         ctx.meta = (R, ld, ns, L, training)
         # a layer's dW may be queued (dw_job) only if nothing but view ops sits between this node and the
         # parameter: a torch.cat / index op in between (padded first-layer weights) would read the still empty
         # gradient when the node returns
-        ctx.defer_ok = [_plain_parameter(tensors[7 * l]) for l in range(L)]
-        ctx.leaf_keys = [_leaf_key(tensors[7 * l]) if ok else None for l, ok in enumerate(ctx.defer_ok)]
-        ctx.store16 = store16
-        ctx.noy = noy
-        ctx.x4 = x4
-        ctx.mode = _COMPUTE_MODE          # the no-store forms keep no Y to fall back on: the backward needs this mode
-        ctx.geo = None
-        if geo is not None:
-            ctx.geo = (g_xyz, g_center, g_off, g_rows, float(g_radius), int(bool(g_norm)))
+        ctx.defer_ok = [_plain_parameter(lay.W) for lay in layers]
+        ctx.leaf_keys = [_leaf_key(lay.W) if ok else None for lay, ok in zip(layers, ctx.defer_ok)]
+        ctx.plan = plan                   # (plan.mode: the no-store forms keep no Y to fall back on, the backward needs this mode)
+        ctx.geo = None if geo is None else (g_xyz, g_center, g_off, g_rows, float(g_radius), int(bool(g_norm)))
         ctx.mark_non_differentiable(arg)
         return out
 
@@ -1347,12 +1366,13 @@ class _SharedMLPPool(Function):
     @once_differentiable
     def backward(ctx, grad_out):
         R, ld, ns, L, training = ctx.meta
+        plan = ctx.plan
         if not training:
             raise RuntimeError("shared_mlp_pool backward is only defined in training mode")
-        if (ctx.noy or ctx.x4) and _COMPUTE_MODE != ctx.mode:
+        if (plan.noy or plan.x4) and _COMPUTE_MODE != plan.mode:
             raise RuntimeError("shared_mlp_pool: the forward ran in compute mode %d and did not store the rows the "
                                "backward of mode %d reads (no-store forms); keep ops.set_compute_dtype unchanged "
-                               "between a forward and its backward" % (ctx.mode, _COMPUTE_MODE))
+                               "between a forward and its backward" % (plan.mode, _COMPUTE_MODE))
         saved = ctx.saved_tensors
         x, arg = saved[0], saved[1]
         Ys, sss, mis = saved[2:2 + L], saved[2 + L:2 + 2 * L], saved[2 + 2 * L:2 + 3 * L]
@@ -1361,55 +1381,48 @@ class _SharedMLPPool(Function):
         dev, st = x.device, _stream()
         dP = grad_out.contiguous()
         G = None
-        grads = [None] * (7 * L)
+        grads = [(None,) * 7] * L         # per layer, in _Layer order
         dx = dxyz = dcenter = None
+        fuse_first, forms = _bwd_forms(plan, R, ld, ns, [tuple(W.shape) for W in Ws], ctx.needs_input_grad[0],
+                                       ctx.geo is not None)
         # BN reductions go through the self-cleaning fp64 accumulator; the weight gradients of all
         # layers share one zero-filled fp32 workspace
-        # SA1-like stacks (4-float input rows, no input gradient, >= 3 layers): layer 0's backward is
-        # taken from the output tile of layer 1's dx GEMM, whose (R x N0) result is never stored
-        fuse_first = (ctx.geo is None and L >= 3 and not ctx.needs_input_grad[0] and ld == 4
-                      and Ws[0].shape[0] <= 64 and Ws[0].shape[0] % 4 == 0 and not _NO_FIRST_FUSE)
         n64 = 2 * sum(W.shape[0] for W in Ws) + (10 * Ws[0].shape[0] + 4 if fuse_first else 0)
         if ctx.geo is not None:
             n64 = max(n64, 24 * Ws[0].shape[0])      # (the factored first layer's dWx totals: every sum above is consumed by then)
-        ws64 = _accum64(n64, dev)
+        ws64 = _Bump(_accum64(n64, dev)[:n64])
         # (+ room for the exact-zero gradients of conv biases shadowed by BatchNorm)
         nbias = sum(W.shape[0] for W, bs in zip(Ws, ctx.bias_shapes) if bs is not None)
-        ws32 = zeros(sum(W.numel() for W in Ws) + nbias, dev)
-        o64 = o32 = 0
+        ws32 = _Bump(zeros(sum(W.numel() for W in Ws) + nbias, dev))
         g12_pending = None
         vec_ready = None      # layer l's sums taken by the dx launch of layer l+1 (RED epilogue), whose last
         #                       workgroup also formed the backward vectors (vec6, dgamma, dbeta)
-        for l in range(L - 1, -1, -1):
+        for l, (form, variant, first_tail) in forms.items():
             W = Ws[l]
             N, K = W.shape
+            sparse = G is None              # (the pooled gradient: the last layer only)
+            sdP, sarg = (dP, arg) if sparse else (None, None)
             if vec_ready is not None:
-                # formed by the last workgroup of the launch that produced this layer's sums
-                vec6, dgamma, dbeta = vec_ready
-                vec_ready = None
-                if g12_pending is not None:          # (A/B: the producer left the sums, vectors as a launch)
-                    _ffi.call("demf_bn_bwd_vectors", N, R, _p(g12_pending), _p(gammas[l]), _p(sss[l]),
-                              _p(mis[l]), _p(vec6), _p(dgamma), _p(dbeta), st)
-                    g12_pending = None
+                # formed by the last workgroup of the launch that produced this layer's sums - or
+                # (A/B: g12_pending) that producer left the sums, and the vectors are a launch
+                (vec6, dgamma, dbeta), vec_ready = vec_ready, None
+                g12, g12_pending = g12_pending, None
             else:
-                vec6 = torch.empty(5 * N, dtype=torch.float32, device=dev)
-                dgamma = torch.empty(N, dtype=torch.float32, device=dev)
-                dbeta = torch.empty(N, dtype=torch.float32, device=dev)
-                g12 = ws64[o64:o64 + 2 * N]
-                o64 += 2 * N
-                if G is None and (_VEC_FIN & 1):
+                vec6, dgamma, dbeta = _bwd_vectors(N, dev)
+                g12 = ws64.take(2 * N)
+                if sparse and (_VEC_FIN & 1):
                     # pooled last layer: sums + vectors in one launch
                     _ffi.call("demf_bn_bwd_reduce_vectors", R, N, ns, _p(dP), _p(arg),
-                              _p(Ys[l]) if Ys[l].numel() else None, _p(yraw),
-                              _p(sss[l]), _p(mis[l]), _p(g12), _p(gammas[l]), _p(vec6), _p(dgamma),
-                              _p(dbeta), int(Ys[l].dtype == torch.bfloat16), st)
+                              _p(Ys[l]) if Ys[l].numel() else None, _p(yraw), _p(sss[l]), _p(mis[l]), _p(g12),
+                              _p(gammas[l]), _p(vec6), _p(dgamma), _p(dbeta), int(Ys[l].dtype == torch.bfloat16), st)
+                    g12 = None
                 else:
-                    _ffi.call("demf_bn_bwd_reduce", R, N, ns, _p(G), _p(dP if G is None else None),
-                              _p(arg if G is None else None), _p(Ys[l]), _p(yraw if G is None else None),
-                              _p(sss[l]), _p(mis[l]), _p(g12), st)
-                    _ffi.call("demf_bn_bwd_vectors", N, R, _p(g12), _p(gammas[l]), _p(sss[l]), _p(mis[l]),
-                              _p(vec6), _p(dgamma), _p(dbeta), st)
-            if l == 0 and ctx.geo is not None:
+                    _ffi.call("demf_bn_bwd_reduce", R, N, ns, _p(G), _p(sdP), _p(sarg), _p(Ys[l]),
+                              _p(yraw if sparse else None), _p(sss[l]), _p(mis[l]), _p(g12), st)
+            if g12 is not None:
+                _ffi.call("demf_bn_bwd_vectors", N, R, _p(g12), _p(gammas[l]), _p(sss[l]), _p(mis[l]),
+                          _p(vec6), _p(dgamma), _p(dbeta), st)
+            if form == "geo_first":
                 # factored first layer: dU per source point through the inverse lists, then the
                 # feature half of dW and the input gradient are GEMMs over the source points
                 g_xyz, g_center, g_off, g_rows, g_radius, g_norm = ctx.geo
@@ -1421,210 +1434,163 @@ class _SharedMLPPool(Function):
                 dU = torch.empty((gB * gN, N), dtype=torch.float32, device=dev)
                 # both halves of dW0 (N, K) = [xyz columns | feature columns] land in place in the
                 # zero-filled workspace: no transposed copies, no concatenation
-                dW0 = ws32[o32:o32 + N * K].view(N, K)
-                o32 += N * K
-                dxyz = dcenter = None
+                dW0 = ws32.take(N * K).view(N, K)
                 if ctx.needs_input_grad[6] or ctx.needs_input_grad[7]:
                     # the coordinates carry a gradient too (vote aggregation)
                     dxyz = torch.empty((gB, gN, 3), dtype=torch.float32, device=dev)
                     dcenter = zeros((gB, gM, 3), dev)
-                _ffi.call("demf_group_first_bwd", gB, gN, gM, ns, N, g_radius, g_norm, _p(g_xyz),
-                          _p(g_center), _p(G), _p(Ys[0]), _p(getattr(ctx, "geo_U", None)), _p(vec6), _p(g_off),
-                          _p(g_rows), _p(dU),
-                          _p(dW0), K, _p(W), K, _p(dxyz), _p(dcenter), _p(ws64[:24 * N]), st)
+                # (the dWx totals reuse the head of the fp64 accumulator: every sum above is consumed by now)
+                _ffi.call("demf_group_first_bwd", gB, gN, gM, ns, N, g_radius, g_norm, _p(g_xyz), _p(g_center), _p(G),
+                          _p(Ys[0]), _p(ctx.geo_U), _p(vec6), _p(g_off), _p(g_rows), _p(dU), _p(dW0), K, _p(W), K,
+                          _p(dxyz), _p(dcenter), _p(ws64.buf[:24 * N]), st)
                 # dWf = dU^T . feat: long thin reduction -> the slab-split dW kernel, identity prologue
                 C0 = K - 3
                 dw_job(gB * gN, N, C0, C0, dU, None, None, 1, dU, _identity_dy_vectors(N, dev), x, None, dW0, K,
                        dw_off=3, defer=ctx.defer_ok[0], leaf=ctx.leaf_keys[0])
-                grads[0] = dW0
-                grads[1], grads[2] = dgamma, dbeta
-                if ctx.bias_shapes[0] is not None:
-                    grads[5] = ws32[o32:o32 + N].view(ctx.bias_shapes[0])
-                    o32 += N
+                grads[0] = _layer_grads(dW0, dgamma, dbeta, ctx.bias_shapes[0], ws32)
                 if ctx.needs_input_grad[0]:
                     from . import fused
                     dx = torch.empty((gB * gN, C0), dtype=torch.float32, device=dev)
                     fused.gemm(gB * gN, C0, N, _p(dU), (N, 1), W.data_ptr() + 12, (1, K), _p(dx), C0)
                 break
-            xprev = Ys[l - 1] if l > 0 else x
-            ldx = xprev.shape[1]
-            dW = ws32[o32:o32 + N * K].view(N, K)
-            o32 += N * K
-            sparse = G is None
-            first_here = l == 1 and fuse_first
-            s16 = getattr(ctx, "store16", False)
-            if l == L - 1 and getattr(ctx, "noy", False):
+            dW = ws32.take(N * K).view(N, K)
+            grads[l] = _layer_grads(dW, dgamma, dbeta, ctx.bias_shapes[l], ws32)
+            dy = (_p(G), _p(sdP), _p(sarg), ns, _p(Ys[l]), _p(vec6))     # the incoming gradient, as the kernels take it
+            below = (_p(Ys[l - 1]), _p(sss[l - 1]), _p(mis[l - 1])) if l > 0 else None
+            dX = None
+            if form == "two_launch":
+                xprev = Ys[l - 1] if l > 0 else x
+                dw_job(R, N, K, xprev.shape[1], G, sdP, sarg, ns, Ys[l], vec6, xprev, sss[l - 1] if l > 0 else None,
+                       dW, K, defer=ctx.defer_ok[l], leaf=ctx.leaf_keys[l])
+            if form == "fused_first" or first_tail:
+                # layer 1 of an SA1-like stack ends the backward: the raw sums of layer 0's whole backward
+                # come out of its pass (fused) or its dx GEMM's output tiles (two launches); no dX
+                sums = ws64.take(10 * K + 4)
+                if first_tail:
+                    _ffi.call("demf_mlp_gemm_bwd_dx_first", R, N, K, _p(G), _p(Ys[1]), _p(vec6), _p(W),
+                              _p(x), *below, _p(sums), st)
+                elif variant == "x4":
+                    _ffi.call("demf_mlp_bwd_fused_x4", R, N, K, _p(G), _p(Ys[l]), _p(vec6), _p(W), _p(x),
+                              _p(Ws[0]), _p(sss[0]), _p(mis[0]), _p(dW), _p(sums), st)
+                else:
+                    _ffi.call("demf_mlp_bwd_fused", R, N, K, *dy, _p(W), *below, None, _p(dW), None, _p(x),
+                              _p(sums), None, None, None, None, 2 if plan.store16 else 0, st)
+                grads[0] = _first_finish(R, K, sums, gammas[0], mis[0], ctx.bias_shapes[0], ws32, dev, st)
+                break
+            if form != "two_launch" or variant in ("dx_red_v", "dx_red"):
+                # the launch also takes layer l-1's BN-backward sums on the way (no separate reduce pass)
+                dX, g12p, vec_ready, fin, g12_pending = _sums_below(
+                    R, K, ws64, gammas[l - 1], dev, vectors={"dx_red_v": True, "dx_red": False}.get(variant),
+                    dx_dtype=torch.bfloat16 if form == "fused" and plan.store16 else torch.float32)
+            elif variant is not None:
+                dX = torch.empty((R, K), dtype=torch.float32, device=dev)
+            if form == "pool_noy":
                 # pooled last layer whose output was never stored: dX, dW and layer l-1's sums from its
                 # INPUT activations and the sparse pooled gradient (csrc/mlp_bwd.hip mlp_bwd_pool_kernel)
-                grads[7 * l], grads[7 * l + 1], grads[7 * l + 2] = dW, dgamma, dbeta
-                if ctx.bias_shapes[l] is not None:
-                    grads[7 * l + 5] = ws32[o32:o32 + N].view(ctx.bias_shapes[l])
-                    o32 += N
-                dX = torch.empty((R, K), dtype=torch.float32, device=dev)
-                g12p = ws64[o64:o64 + 2 * K]
-                o64 += 2 * K
-                vec_ready = (torch.empty(5 * K, dtype=torch.float32, device=dev),
-                             torch.empty(K, dtype=torch.float32, device=dev),
-                             torch.empty(K, dtype=torch.float32, device=dev))
                 nws = ctypes.c_longlong()
                 _ffi.call("demf_mlp_bwd_pool_ws", R, ctypes.addressof(nws))
                 wsp = torch.empty(nws.value, dtype=torch.float32, device=dev)
                 _ffi.call("demf_mlp_bwd_pool", R, N, K, ns, _p(dP), _p(arg), _p(yraw), _p(vec6), _p(W),
-                          _p(Ys[l - 1]), _p(sss[l - 1]), _p(mis[l - 1]), _p(dX), _p(dW), _p(g12p),
-                          _p(gammas[l - 1]) if (_VEC_FIN & 2) else None, _p(vec_ready[0]), _p(vec_ready[1]),
-                          _p(vec_ready[2]), _p(wsp), st)
-                if not (_VEC_FIN & 2):
-                    g12_pending = g12p
-                G = dX
-                continue
-            if l > 0 and ldx == K and _bwd_fused_ok(N, K, ns, sparse, first_here):
-                # ONE pass over Y_l: dX (or, for SA1's layer 1, the raw sums of layer 0's whole
-                # backward instead of dX), dW and layer l-1's BN-backward sums (csrc/mlp_bwd.hip)
-                grads[7 * l], grads[7 * l + 1], grads[7 * l + 2] = dW, dgamma, dbeta
-                if ctx.bias_shapes[l] is not None:
-                    grads[7 * l + 5] = ws32[o32:o32 + N].view(ctx.bias_shapes[l])
-                    o32 += N
-                if first_here:
-                    N0 = K
-                    sums = ws64[o64:o64 + 10 * N0 + 4]
-                    o64 += 10 * N0 + 4
-                    if getattr(ctx, "x4", False):
-                        _ffi.call("demf_mlp_bwd_fused_x4", R, N, K, _p(G), _p(Ys[l]), _p(vec6), _p(W), _p(x),
-                                  _p(Ws[0]), _p(sss[0]), _p(mis[0]), _p(dW), _p(sums), st)
-                    else:
-                        _ffi.call("demf_mlp_bwd_fused", R, N, K, _p(G), None, None, ns, _p(Ys[l]), _p(vec6),
-                                  _p(W), _p(Ys[0]), _p(sss[0]), _p(mis[0]), None, _p(dW), None, _p(x),
-                                  _p(sums), None, None, None, None, 2 if s16 else 0, st)
-                    dW0 = ws32[o32:o32 + N0 * 4].view(N0, 4)
-                    o32 += N0 * 4
-                    dgamma0 = torch.empty(N0, dtype=torch.float32, device=dev)
-                    dbeta0 = torch.empty(N0, dtype=torch.float32, device=dev)
-                    _ffi.call("demf_mlp_first_finish", N0, R, _p(sums), _p(gammas[0]), _p(mis[0]),
-                              _p(dW0), _p(dgamma0), _p(dbeta0), st)
-                    grads[0], grads[1], grads[2] = dW0, dgamma0, dbeta0
-                    if ctx.bias_shapes[0] is not None:
-                        grads[5] = ws32[o32:o32 + N0].view(ctx.bias_shapes[0])
-                        o32 += N0
-                    break
-                dX = torch.empty((R, K), dtype=torch.bfloat16 if s16 else torch.float32, device=dev)
-                g12p = ws64[o64:o64 + 2 * K]
-                o64 += 2 * K
-                vec_ready = (torch.empty(5 * K, dtype=torch.float32, device=dev),
-                             torch.empty(K, dtype=torch.float32, device=dev),
-                             torch.empty(K, dtype=torch.float32, device=dev))
-                _ffi.call("demf_mlp_bwd_fused", R, N, K, _p(G), _p(dP if sparse else None),
-                          _p(arg if sparse else None), ns, _p(Ys[l]), _p(vec6), _p(W), _p(Ys[l - 1]),
-                          _p(sss[l - 1]), _p(mis[l - 1]), _p(dX), _p(dW), _p(g12p), None, None,
-                          _p(gammas[l - 1]) if (_VEC_FIN & 2) else None, _p(vec_ready[0]), _p(vec_ready[1]),
-                          _p(vec_ready[2]), 3 if s16 else 0, st)
-                if not (_VEC_FIN & 2):
-                    g12_pending = g12p
-                G = dX
-                continue
-            if l > 0 and ldx == K and not first_here and not s16 and _bwd_fused_cols_ok(R, N, K, ns, sparse):
-                # the one-pass backward per 128-column chunk of a wider layer l-1 (vote aggregation:
-                # 256 -> 256 on 32 768 rows): each launch yields its columns of dX and dW, the sums and
-                # (last workgroup) the vectors of those channels
-                grads[7 * l], grads[7 * l + 1], grads[7 * l + 2] = dW, dgamma, dbeta
-                if ctx.bias_shapes[l] is not None:
-                    grads[7 * l + 5] = ws32[o32:o32 + N].view(ctx.bias_shapes[l])
-                    o32 += N
-                dX = torch.empty((R, K), dtype=torch.float32, device=dev)
-                g12p = ws64[o64:o64 + 2 * K]
-                o64 += 2 * K
-                vec_ready = (torch.empty(5 * K, dtype=torch.float32, device=dev),
-                             torch.empty(K, dtype=torch.float32, device=dev),
-                             torch.empty(K, dtype=torch.float32, device=dev))
+                          *below, _p(dX), _p(dW), _p(g12p), *fin, _p(wsp), st)
+            elif form == "fused":
+                # ONE pass over Y_l: dX, dW and layer l-1's BN-backward sums (csrc/mlp_bwd.hip)
+                _ffi.call("demf_mlp_bwd_fused", R, N, K, *dy, _p(W), *below, _p(dX), _p(dW), _p(g12p), None, None,
+                          *fin, 3 if plan.store16 else 0, st)
+            elif form == "fused_cols":
+                # ... per 128-column chunk of a wider layer l-1 (vote aggregation: 256 -> 256 on 32 768 rows): each
+                # launch yields its columns of dX and dW, the sums and (last workgroup) the vectors of those channels
                 for c0 in range(0, K, 128):
-                    _ffi.call("demf_mlp_bwd_fused_cols", R, N, K, c0, 128, _p(G), _p(dP if sparse else None),
-                              _p(arg if sparse else None), ns, _p(Ys[l]), _p(vec6), _p(W), _p(Ys[l - 1]),
-                              _p(sss[l - 1]), _p(mis[l - 1]), _p(dX), _p(dW), _p(g12p),
-                              _p(gammas[l - 1]) if (_VEC_FIN & 2) else None, _p(vec_ready[0]),
-                              _p(vec_ready[1]), _p(vec_ready[2]), st)
-                if not (_VEC_FIN & 2):
-                    g12_pending = g12p
+                    _ffi.call("demf_mlp_bwd_fused_cols", R, N, K, c0, 128, *dy, _p(W), *below, _p(dX), _p(dW),
+                              _p(g12p), *fin, st)
+            elif form == "fused_wide":
+                # ... as ONE launch over all the column chunks
+                _ffi.call("demf_mlp_bwd_fused_wide", R, N, K, *dy, _p(W), *below, _p(dX), _p(dW), _p(g12p), *fin, st)
+            elif variant == "dx_red_v":
+                _ffi.call("demf_mlp_gemm_bwd_dx_red_v", R, N, K, K, *dy, _p(W), _p(dX), *below, _p(g12p), *fin, st)
+            elif variant == "dx_red":
+                _ffi.call("demf_mlp_gemm_bwd_dx_red", R, N, K, K, *dy, _p(W), _p(dX), *below, _p(g12p), st)
+            elif variant == "dx_w":
+                # W read as it is: the kernel transposes the slab on its way into LDS
+                _ffi.call("demf_mlp_gemm_bwd_dx_w", R, N, K, K, *dy, _p(W), _p(dX), st)
+            elif variant == "dx":
+                Wtt = W.t().contiguous()
+                _ffi.call("demf_mlp_gemm_bwd_dx", R, N, K, K, *dy, _p(Wtt), _p(dX), st)
+            if l > 0:
                 G = dX
-                continue
-            if l > 0 and ldx == K and not first_here and not s16 and _bwd_fused_wide_ok(R, N, K, ns, sparse):
-                # ... as ONE launch over all the column chunks: dX, dW, the sums and (last workgroup of the
-                # launch) the vectors of every channel of layer l-1
-                grads[7 * l], grads[7 * l + 1], grads[7 * l + 2] = dW, dgamma, dbeta
-                if ctx.bias_shapes[l] is not None:
-                    grads[7 * l + 5] = ws32[o32:o32 + N].view(ctx.bias_shapes[l])
-                    o32 += N
-                dX = torch.empty((R, K), dtype=torch.float32, device=dev)
-                g12p = ws64[o64:o64 + 2 * K]
-                o64 += 2 * K
-                vec_ready = (torch.empty(5 * K, dtype=torch.float32, device=dev),
-                             torch.empty(K, dtype=torch.float32, device=dev),
-                             torch.empty(K, dtype=torch.float32, device=dev))
-                _ffi.call("demf_mlp_bwd_fused_wide", R, N, K, _p(G), _p(dP if sparse else None),
-                          _p(arg if sparse else None), ns, _p(Ys[l]), _p(vec6), _p(W), _p(Ys[l - 1]),
-                          _p(sss[l - 1]), _p(mis[l - 1]), _p(dX), _p(dW), _p(g12p),
-                          _p(gammas[l - 1]) if (_VEC_FIN & 2) else None, _p(vec_ready[0]),
-                          _p(vec_ready[1]), _p(vec_ready[2]), st)
-                if not (_VEC_FIN & 2):
-                    g12_pending = g12p
-                G = dX
-                continue
-            dw_job(R, N, K, ldx, G, dP if sparse else None, arg if sparse else None, ns, Ys[l], vec6, xprev,
-                   sss[l - 1] if l > 0 else None, dW, K, defer=ctx.defer_ok[l], leaf=ctx.leaf_keys[l])
-            grads[7 * l], grads[7 * l + 1], grads[7 * l + 2] = dW, dgamma, dbeta
-            if ctx.bias_shapes[l] is not None:
-                grads[7 * l + 5] = ws32[o32:o32 + N].view(ctx.bias_shapes[l])
-                o32 += N
-            if l == 1 and fuse_first:
-                N0 = K
-                sums = ws64[o64:o64 + 10 * N0 + 4]
-                o64 += 10 * N0 + 4
-                _ffi.call("demf_mlp_gemm_bwd_dx_first", R, N, N0, _p(G), _p(Ys[1]), _p(vec6), _p(W),
-                          _p(x), _p(Ys[0]), _p(sss[0]), _p(mis[0]), _p(sums), st)
-                dW0 = ws32[o32:o32 + N0 * 4].view(N0, 4)
-                o32 += N0 * 4
-                dgamma0 = torch.empty(N0, dtype=torch.float32, device=dev)
-                dbeta0 = torch.empty(N0, dtype=torch.float32, device=dev)
-                _ffi.call("demf_mlp_first_finish", N0, R, _p(sums), _p(gammas[0]), _p(mis[0]),
-                          _p(dW0), _p(dgamma0), _p(dbeta0), st)
-                grads[0], grads[1], grads[2] = dW0, dgamma0, dbeta0
-                if ctx.bias_shapes[0] is not None:
-                    grads[5] = ws32[o32:o32 + N0].view(ctx.bias_shapes[0])
-                    o32 += N0
-                break
-            if l > 0 or ctx.needs_input_grad[0]:
-                dX = torch.empty((R, K), dtype=torch.float32, device=dev)
-                if K % 4 == 0 and l > 0 and not _NO_RED_FUSE:
-                    # + layer l-1's BN-backward sums from the output tiles (no separate reduce pass)
-                    g12p = ws64[o64:o64 + 2 * K]
-                    o64 += 2 * K
-                    vec_ready = (torch.empty(5 * K, dtype=torch.float32, device=dev),
-                                 torch.empty(K, dtype=torch.float32, device=dev),
-                                 torch.empty(K, dtype=torch.float32, device=dev))
-                    if _VEC_FIN & 4:
-                        _ffi.call("demf_mlp_gemm_bwd_dx_red_v", R, N, K, K, _p(G), _p(dP if sparse else None),
-                                  _p(arg if sparse else None), ns, _p(Ys[l]), _p(vec6), _p(W), _p(dX),
-                                  _p(Ys[l - 1]), _p(sss[l - 1]), _p(mis[l - 1]), _p(g12p), _p(gammas[l - 1]),
-                                  _p(vec_ready[0]), _p(vec_ready[1]), _p(vec_ready[2]), st)
-                    else:
-                        _ffi.call("demf_mlp_gemm_bwd_dx_red", R, N, K, K, _p(G), _p(dP if sparse else None),
-                                  _p(arg if sparse else None), ns, _p(Ys[l]), _p(vec6), _p(W), _p(dX),
-                                  _p(Ys[l - 1]), _p(sss[l - 1]), _p(mis[l - 1]), _p(g12p), st)
-                        g12_pending = g12p
-                elif K % 4 == 0:
-                    # W read as it is: the kernel transposes the slab on its way into LDS
-                    _ffi.call("demf_mlp_gemm_bwd_dx_w", R, N, K, K, _p(G), _p(dP if sparse else None),
-                              _p(arg if sparse else None), ns, _p(Ys[l]), _p(vec6), _p(W), _p(dX), st)
-                else:
-                    Wtt = W.t().contiguous()
-                    _ffi.call("demf_mlp_gemm_bwd_dx", R, N, K, K, _p(G), _p(dP if sparse else None),
-                              _p(arg if sparse else None), ns, _p(Ys[l]), _p(vec6), _p(Wtt), _p(dX),
-                              st)
-                if l > 0:
-                    G = dX
-                else:
-                    dx = dX
+            else:
+                dx = dX
         return (dx, None, None, None, None, None,
                 dxyz if ctx.needs_input_grad[6] else None,
-                dcenter if ctx.needs_input_grad[7] else None, *grads)
+                dcenter if ctx.needs_input_grad[7] else None, *[g for lg in grads for g in lg])
+
+
+class _Bump:
+    """Pieces of a workspace, cut in order.  Asking for more than is left raises: a sizing mistake must not reach a
+    kernel as a silently short slice."""
+
+    def __init__(self, buf):
+        self.buf, self.off = buf, 0
+
+    def take(self, n):
+        if self.off + n > self.buf.numel():
+            raise RuntimeError("shared_mlp_pool: workspace of %d elements asked for %d more at %d"
+                               % (self.buf.numel(), n, self.off))
+        self.off += n
+        return self.buf[self.off - n:self.off]
+
+
+def _bn_tail(lay, eps, momentum, ss, mi):
+    """The BatchNorm bookkeeping a training forward launch ends with (its last workgroup finalises the statistics):
+    gamma, beta, eps, momentum, running mean / var, num_batches_tracked, the scale / shift and mean / invstd it
+    writes, and the conv bias that only shifts the running mean."""
+    return (_p(lay.gamma), _p(lay.beta), float(eps), float(momentum), _p(lay.rmean), _p(lay.rvar), _p(lay.nbt),
+            _p(ss), _p(mi), _p(lay.bias))
+
+
+_BN_TAIL_EVAL = (None, None, 0.0, 0.0, None, None, None, None, None, None)      # no bookkeeping
+
+
+def _eval_scale_shift(lay, eps, ss, mi):
+    """Eval mode: scale / shift and mean / invstd from the running statistics."""
+    N = lay.W.shape[0]
+    invstd = torch.rsqrt(lay.rvar + eps)
+    ss[:N] = lay.gamma * invstd
+    ss[N:] = lay.beta - lay.rmean * lay.gamma * invstd
+    mi[:N] = lay.rmean
+    mi[N:] = invstd
+
+
+def _layer_grads(dW, dgamma, dbeta, bias_shape, ws32):
+    """One layer's gradients in _Layer order; a conv bias shadowed by BatchNorm gets exact zeros from the workspace."""
+    dbias = None if bias_shape is None else ws32.take(dW.shape[0]).view(bias_shape)
+    return (dW, dgamma, dbeta, None, None, dbias, None)
+
+
+def _bwd_vectors(N, dev):
+    """vec6 (5 N), dgamma, dbeta of a layer: what demf_bn_bwd_vectors, or the last workgroup of a fused launch, forms."""
+    return tuple(torch.empty(n, dtype=torch.float32, device=dev) for n in (5 * N, N, N))
+
+
+def _sums_below(R, K, ws64, gamma_below, dev, vectors=None, dx_dtype=torch.float32):
+    """What a launch that also reduces the BN-backward sums of the layer below (K channels) writes: dX (R, K), the
+    fp64 sums g12p and - if it is given that layer's gamma (``vectors``; default: _VEC_FIN bit 1) - the vectors, from
+    its last workgroup.  Without gamma the sums stay pending for a demf_bn_bwd_vectors launch.  Returns dX, g12p, the
+    vectors' tensors, the launch's (gamma | NULL, vec6, dgamma, dbeta) arguments and the pending sums (or None)."""
+    if vectors is None:
+        vectors = bool(_VEC_FIN & 2)
+    dX = torch.empty((R, K), dtype=dx_dtype, device=dev)
+    g12p = ws64.take(2 * K)
+    vec = _bwd_vectors(K, dev)
+    return dX, g12p, vec, (_p(gamma_below) if vectors else None, *map(_p, vec)), None if vectors else g12p
+
+
+def _first_finish(R, N0, sums, gamma0, mi0, bias_shape0, ws32, dev, st):
+    """Layer 0 of an SA1-like stack from the raw sums its layer 1 left: dW0 (N0, 4), dgamma0, dbeta0."""
+    dW0 = ws32.take(N0 * 4).view(N0, 4)
+    dgamma0 = torch.empty(N0, dtype=torch.float32, device=dev)
+    dbeta0 = torch.empty(N0, dtype=torch.float32, device=dev)
+    _ffi.call("demf_mlp_first_finish", N0, R, _p(sums), _p(gamma0), _p(mi0), _p(dW0), _p(dgamma0), _p(dbeta0), st)
+    return _layer_grads(dW0, dgamma0, dbeta0, bias_shape0, ws32)
 
 
 def shared_mlp_pool(x, ns, layers, training=True, eps=1e-5, momentum=0.1, geo=None):
