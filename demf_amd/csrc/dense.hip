@@ -15,6 +15,8 @@
 // dW = dY^T.X (both operands M-contiguous along the reduction) are the same kernel; 64x64 block
 // tiles, 4 waves x one 32x32 MFMA accumulator, K staged in steps of 32 through LDS (fragment trick
 // of mlp.hip: a lane feeds component m of its float4 along K to MFMA m).
+#include <initializer_list>
+
 #include "common.h"
 #include <type_traits>
 #include "rng.h"
@@ -992,6 +994,199 @@ __global__ void msda_prep_bwd_k(int R, int Q, int H, int L, int P, const float* 
   dpts[3 * row + 2] = gx * m[2] + gy * m[6] + gw * m[10];
 }
 
+// The two kernels above at the model's widths (H = 8 heads, L = 4 levels, P = 2 points; 16-byte aligned rows),
+// same arithmetic term by term.  A (row, head) item owns 16 consecutive offset floats and 8 consecutive logits:
+// they come in as float4 - every byte of every sector a wave touches is used - and all of a thread's loads, the
+// level constants included, are issued before the first use; the row lives in registers under compile-time
+// indices; dloc / dw (and their optional second contribution) are read once; the sum over the 8 heads of a row
+// goes over 8 neighbouring lanes on DPP (the same pairs as the xor butterfly, so the same bits).
+constexpr int MP_H = 8, MP_L = 4, MP_P = 2, MP_LP = MP_L * MP_P, MP_ROW = MP_H * MP_LP * 3;
+
+__device__ __forceinline__ void ld4(const float* __restrict__ p, float* v) {
+  const float4 x = *reinterpret_cast<const float4*>(p);
+  v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+}
+__device__ __forceinline__ void st4(float* __restrict__ p, const float* v) {
+  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+__global__ __launch_bounds__(256) void msda_prep_fwd_842_k(int R, int Q, const float* __restrict__ pts,
+                                                           const float* __restrict__ M, const float* __restrict__ ab,
+                                                           const float* __restrict__ vr,
+                                                           const long long* __restrict__ shapes,
+                                                           const float* __restrict__ raw, float* __restrict__ loc,
+                                                           float* __restrict__ w, float* __restrict__ uvw) {
+  const int t0 = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = t0 < R * MP_H;
+  const int t = live ? t0 : R * MP_H - 1;
+  const int row = t >> 3, h = t & 7, b = row / Q;
+  float off[2 * MP_LP], lg[MP_LP], m[12], abv[4], vrv[2 * MP_L], iw[MP_L], ih[MP_L];
+  const float* prow = raw + (size_t)row * MP_ROW;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) ld4(prow + h * 2 * MP_LP + 4 * i, off + 4 * i);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) ld4(prow + MP_H * MP_LP * 2 + h * MP_LP + 4 * i, lg + 4 * i);
+  const float x = pts[3 * row], y = pts[3 * row + 1], zc = pts[3 * row + 2];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) m[i] = M[16 * b + i];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) abv[i] = ab[4 * b + i];
+#pragma unroll
+  for (int i = 0; i < 2 * MP_L; ++i) vrv[i] = vr[b * MP_L * 2 + i];
+#pragma unroll
+  for (int l = 0; l < MP_L; ++l) {
+    iw[l] = 1.0f / (float)shapes[2 * l + 1];
+    ih[l] = 1.0f / (float)shapes[2 * l];
+  }
+  const float px = m[0] * x + m[1] * y + m[2] * zc + m[3];
+  const float py = m[4] * x + m[5] * y + m[6] * zc + m[7];
+  const float pw = m[8] * x + m[9] * y + m[10] * zc + m[11];
+  const float u0 = px / pw * abv[0] + abv[1];
+  const float v0 = py / pw * abv[2] + abv[3];
+  const float u = fminf(fmaxf(u0, 0.f), 1.f), v = fminf(fmaxf(v0, 0.f), 1.f);
+  if (live && h == 0) {
+    uvw[4 * row] = u0; uvw[4 * row + 1] = v0; uvw[4 * row + 2] = px / pw; uvw[4 * row + 3] = py / pw;
+  }
+  float mx = -__builtin_inff();
+#pragma unroll
+  for (int i = 0; i < MP_LP; ++i) mx = fmaxf(mx, lg[i]);
+  float e[MP_LP], sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < MP_LP; ++i) { e[i] = __expf(lg[i] - mx); sum += e[i]; }
+  const float inv = 1.0f / sum;
+  float lo[2 * MP_LP], wo[MP_LP];
+#pragma unroll
+  for (int l = 0; l < MP_L; ++l) {
+    const float rx = u * vrv[2 * l], ry = v * vrv[2 * l + 1];
+#pragma unroll
+    for (int q = 0; q < MP_P; ++q) {
+      const int i = l * MP_P + q;
+      lo[2 * i] = rx + off[2 * i] * iw[l];
+      lo[2 * i + 1] = ry + off[2 * i + 1] * ih[l];
+      wo[i] = e[i] * inv;
+    }
+  }
+  if (!live) return;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) st4(loc + (size_t)t * 2 * MP_LP + 4 * i, lo + 4 * i);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) st4(w + (size_t)t * MP_LP + 4 * i, wo + 4 * i);
+}
+
+template <bool SECOND>
+__global__ __launch_bounds__(256) void msda_prep_bwd_842_k(int R, int Q, const float* __restrict__ pts,
+                                                           const float* __restrict__ M, const float* __restrict__ ab,
+                                                           const float* __restrict__ vr,
+                                                           const long long* __restrict__ shapes,
+                                                           const float* __restrict__ w, const float* __restrict__ uvw,
+                                                           const float* __restrict__ dloc,
+                                                           const float* __restrict__ dloc2,
+                                                           const float* __restrict__ dw, const float* __restrict__ dw2,
+                                                           float* __restrict__ draw, float* __restrict__ dpts) {
+  const int t0 = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = t0 < R * MP_H;            // R * 8 items: a dead lane's group of 8 is dead as a whole
+  const int t = live ? t0 : R * MP_H - 1;
+  const int row = t >> 3, h = t & 7, b = row / Q;
+  float dl[2 * MP_LP], dwv[MP_LP], wv[MP_LP], vrv[2 * MP_L], iw[MP_L], ih[MP_L];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) ld4(dloc + (size_t)t * 2 * MP_LP + 4 * i, dl + 4 * i);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) ld4(dw + (size_t)t * MP_LP + 4 * i, dwv + 4 * i);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) ld4(w + (size_t)t * MP_LP + 4 * i, wv + 4 * i);
+  if constexpr (SECOND) {                     // (dloc2, dw2) null or not: each pair decided on its own
+    float s[4];
+    if (dloc2 != nullptr) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        ld4(dloc2 + (size_t)t * 2 * MP_LP + 4 * i, s);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) dl[4 * i + k] = dl[4 * i + k] + s[k];
+      }
+    }
+    if (dw2 != nullptr) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        ld4(dw2 + (size_t)t * MP_LP + 4 * i, s);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) dwv[4 * i + k] = dwv[4 * i + k] + s[k];
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 2 * MP_L; ++i) vrv[i] = vr[b * MP_L * 2 + i];
+#pragma unroll
+  for (int l = 0; l < MP_L; ++l) {
+    iw[l] = 1.0f / (float)shapes[2 * l + 1];
+    ih[l] = 1.0f / (float)shapes[2 * l];
+  }
+  // what the thread of head 0 needs after the sum over heads, fetched with everything else
+  float uv[4] = {0.f, 0.f, 0.f, 0.f}, p3[3] = {0.f, 0.f, 0.f}, m[12], ab0 = 0.f, ab2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) m[i] = 0.f;
+  if (dpts != nullptr) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) uv[i] = uvw[4 * row + i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) p3[i] = pts[3 * row + i];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) m[i] = M[16 * b + i];
+    ab0 = ab[4 * b];
+    ab2 = ab[4 * b + 2];
+  }
+  float dot = 0.f;
+#pragma unroll
+  for (int i = 0; i < MP_LP; ++i) dot = __builtin_fmaf(dwv[i], wv[i], dot);
+  float dof[2 * MP_LP], dlg[MP_LP];
+#pragma unroll
+  for (int l = 0; l < MP_L; ++l)
+#pragma unroll
+    for (int q = 0; q < MP_P; ++q) {
+      const int i = l * MP_P + q;
+      dof[2 * i] = dl[2 * i] * iw[l];
+      dof[2 * i + 1] = dl[2 * i + 1] * ih[l];
+      dlg[i] = wv[i] * (dwv[i] - dot);
+    }
+  if (live) {
+    float* prow = draw + (size_t)row * MP_ROW;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) st4(prow + h * 2 * MP_LP + 4 * i, dof + 4 * i);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) st4(prow + MP_H * MP_LP * 2 + h * MP_LP + 4 * i, dlg + 4 * i);
+  }
+  if (dpts == nullptr) return;
+  float du = 0.f, dv = 0.f;
+#pragma unroll
+  for (int l = 0; l < MP_L; ++l)
+#pragma unroll
+    for (int q = 0; q < MP_P; ++q) {
+      const int i = l * MP_P + q;
+      du = __builtin_fmaf(dl[2 * i], vrv[2 * l], du);
+      dv = __builtin_fmaf(dl[2 * i + 1], vrv[2 * l + 1], dv);
+    }
+  du = group_allsum<MP_H>(du);
+  dv = group_allsum<MP_H>(dv);
+  if (!live || h != 0) return;
+  const float u0 = uv[0], v0 = uv[1], xw = uv[2], yw = uv[3];
+  if (!(u0 >= 0.f && u0 <= 1.f)) du = 0.f;          // torch.clamp passes the gradient on [min, max]
+  if (!(v0 >= 0.f && v0 <= 1.f)) dv = 0.f;
+  const float x = p3[0], y = p3[1], zc = p3[2];
+  const float pw = m[8] * x + m[9] * y + m[10] * zc + m[11];
+  const float gx = du * ab0 / pw, gy = dv * ab2 / pw;                      // d / d(px), d / d(py)
+  const float gw = -(gx * xw + gy * yw);                                   // d / d(pw)
+  dpts[3 * row] = gx * m[0] + gy * m[4] + gw * m[8];
+  dpts[3 * row + 1] = gx * m[1] + gy * m[5] + gw * m[9];
+  dpts[3 * row + 2] = gx * m[2] + gy * m[6] + gw * m[10];
+}
+
+// the fast forms' precondition: every row of every float4-accessed array starts on a 16-byte boundary.  They are
+// launched one wave per workgroup: 16 384 items then spread over 256 workgroups, not 64
+static inline bool all_aligned16(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if (((size_t)p & 15) != 0) return false;
+  return true;
+}
+
 // ---- row L2 normalisation (VoteModule norm_feats) -------------------------------------------------------
 template <int VPL>
 __global__ __launch_bounds__(256) void l2norm_fwd_k(int R, const float* __restrict__ x,
@@ -1352,8 +1547,12 @@ extern "C" int demf_msda_prep_fwd(int R, int Q, int H, int L, int P, const float
   DEMF_REQUIRE(R > 0 && Q > 0 && R % Q == 0 && H > 0 && L > 0 && P > 0 && L * P <= 16,
                "msda_prep_fwd: bad sizes (L*P <= 16)");
   DEMF_REQUIRE(pts && M && ab && valid_ratios && shapes && raw && loc && w && uvw, "msda_prep_fwd: null pointer");
-  hipLaunchKernelGGL(msda_prep_fwd_k, dim3(cdiv(R * H, 256)), dim3(256), 0, (hipStream_t)stream, R, Q, H, L,
-                     P, pts, M, ab, valid_ratios, (const long long*)shapes, raw, loc, w, uvw);
+  if (H == MP_H && L == MP_L && P == MP_P && all_aligned16({raw, loc, w}))
+    hipLaunchKernelGGL(msda_prep_fwd_842_k, dim3(cdiv(R * H, 64)), dim3(64), 0, (hipStream_t)stream, R, Q, pts, M,
+                       ab, valid_ratios, (const long long*)shapes, raw, loc, w, uvw);
+  else
+    hipLaunchKernelGGL(msda_prep_fwd_k, dim3(cdiv(R * H, 256)), dim3(256), 0, (hipStream_t)stream, R, Q, H, L,
+                       P, pts, M, ab, valid_ratios, (const long long*)shapes, raw, loc, w, uvw);
   return check_launch("msda_prep_fwd_k");
 }
 
@@ -1365,8 +1564,17 @@ extern "C" int demf_msda_prep_bwd(int R, int Q, int H, int L, int P, const float
   DEMF_REQUIRE(R > 0 && Q > 0 && R % Q == 0 && H > 0 && L > 0 && P > 0 && L * P <= 16,
                "msda_prep_bwd: bad sizes (L*P <= 16)");
   DEMF_REQUIRE(pts && M && ab && valid_ratios && shapes && w && uvw && dloc && dw && draw, "msda_prep_bwd: null pointer");
-  hipLaunchKernelGGL(msda_prep_bwd_k, dim3(cdiv(R * H, 256)), dim3(256), 0, (hipStream_t)stream, R, Q, H, L,
-                     P, pts, M, ab, valid_ratios, (const long long*)shapes, w, uvw, dloc, dloc2, dw, dw2, draw, dpts);
+  if (H == MP_H && L == MP_L && P == MP_P && all_aligned16({w, dloc, dloc2, dw, dw2, draw})) {
+    if (dloc2 != nullptr || dw2 != nullptr)
+      hipLaunchKernelGGL(msda_prep_bwd_842_k<true>, dim3(cdiv(R * H, 64)), dim3(64), 0, (hipStream_t)stream, R, Q,
+                         pts, M, ab, valid_ratios, (const long long*)shapes, w, uvw, dloc, dloc2, dw, dw2, draw, dpts);
+    else
+      hipLaunchKernelGGL(msda_prep_bwd_842_k<false>, dim3(cdiv(R * H, 64)), dim3(64), 0, (hipStream_t)stream, R, Q,
+                         pts, M, ab, valid_ratios, (const long long*)shapes, w, uvw, dloc, dloc2, dw, dw2, draw, dpts);
+  } else {
+    hipLaunchKernelGGL(msda_prep_bwd_k, dim3(cdiv(R * H, 256)), dim3(256), 0, (hipStream_t)stream, R, Q, H, L,
+                       P, pts, M, ab, valid_ratios, (const long long*)shapes, w, uvw, dloc, dloc2, dw, dw2, draw, dpts);
+  }
   return check_launch("msda_prep_bwd_k");
 }
 

@@ -34,17 +34,58 @@ __device__ __forceinline__ float smooth_l1_grad(float d, float beta) {
   return a < beta ? d / beta : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
 }
 
-// log-softmax cross entropy over n logits at p; returns loss, optionally writes softmax-onehot
-template <int MAXN>
-__device__ __forceinline__ float ce(const float* p, int n, int t, float* grad /*nullable*/, float gscale) {
+// log-softmax cross entropy over the N logits of a register array; returns the loss, optionally adds
+// gscale * (softmax - onehot) to grad.  Every index is a compile-time constant after unrolling (the target is
+// picked by selects), so the row never goes to scratch memory.
+template <int N>
+__device__ __forceinline__ float ce_reg(const float* p, int t, float* grad /*nullable*/, float gscale) {
   float m = p[0];
-  for (int i = 1; i < n; ++i) m = fmaxf(m, p[i]);
+#pragma unroll
+  for (int i = 1; i < N; ++i) m = fmaxf(m, p[i]);
   float s = 0.f;
-  for (int i = 0; i < n; ++i) s += __expf(p[i] - m);
+#pragma unroll
+  for (int i = 0; i < N; ++i) s += __expf(p[i] - m);
   const float lse = m + __logf(s);
-  if (grad)
-    for (int i = 0; i < n; ++i) grad[i] += gscale * (__expf(p[i] - lse) - (i == t ? 1.f : 0.f));
-  return lse - p[t];
+  float pt = p[0];
+#pragma unroll
+  for (int i = 1; i < N; ++i) pt = i == t ? p[i] : pt;
+  if (grad) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) grad[i] += gscale * (__expf(p[i] - lse) - (i == t ? 1.f : 0.f));
+  }
+  return lse - pt;
+}
+
+// v[j] of a 12-element register array, j in 0..11
+__device__ __forceinline__ float pick12(const float* v, int j) {
+  float r = v[0];
+#pragma unroll
+  for (int i = 1; i < 12; ++i) r = i == j ? v[i] : r;
+  return r;
+}
+
+// sum over the wave on DPP, returned wave-uniform (row sums, then row_bcast:15 / row_bcast:31 into lane 63)
+__device__ __forceinline__ float wave_sum(float v) {
+  v += dpp_f32<0xB1>(v, v);            // quad_perm [1,0,3,2]
+  v += dpp_f32<0x4E>(v, v);            // quad_perm [2,3,0,1]
+  v += dpp_f32<0x141>(v, v);           // row_half_mirror
+  v += dpp_f32<0x140>(v, v);           // row_mirror: every lane holds its row's sum
+  v += dpp_f32<0x142, 0xA>(0.f, v);    // row_bcast:15 -> rows 1,3 (rows 0,2 add 0)
+  v += dpp_f32<0x143, 0xC>(0.f, v);    // row_bcast:31 -> rows 2,3
+  return readlane_f(v, 63);
+}
+template <int CTRL, int ROW_MASK = 0xF>
+__device__ __forceinline__ int dpp_i32(int old, int v) {
+  return __builtin_amdgcn_update_dpp(old, v, CTRL, ROW_MASK, 0xF, false);
+}
+__device__ __forceinline__ int wave_sum_i(int v) {
+  v += dpp_i32<0xB1>(v, v);
+  v += dpp_i32<0x4E>(v, v);
+  v += dpp_i32<0x141>(v, v);
+  v += dpp_i32<0x140>(v, v);
+  v += dpp_i32<0x142, 0xA>(0, v);
+  v += dpp_i32<0x143, 0xC>(0, v);
+  return readlane_i(v, 63);
 }
 
 struct IoU {
@@ -57,6 +98,7 @@ struct IoU {
 __device__ __forceinline__ IoU aa_iou(const float* c, const float* s, const float* ct, const float* st) {
   IoU r;
   float a1 = 1.f, a2 = 1.f, ov = 1.f;
+#pragma unroll
   for (int k = 0; k < 3; ++k) {
     const float l1 = c[k] - s[k] * 0.5f, h1 = c[k] + s[k] * 0.5f;
     const float l2 = ct[k] - st[k] * 0.5f, h2 = ct[k] + st[k] * 0.5f;
@@ -78,55 +120,129 @@ __device__ __forceinline__ IoU aa_iou(const float* c, const float* s, const floa
   return r;
 }
 
-// one thread per proposal row; block-reduce the 7 partial sums; fp32 atomics into out[7]
-__global__ __launch_bounds__(256) void head_loss_fwd_k(
+// ---- proposal rows through LDS ------------------------------------------------------------------
+// A tile of T rows of W floats is one contiguous run of T * W floats: the workgroup reads it with lane-consecutive
+// dwords (all of a thread's loads issued before the first use), parks it in LDS at an ODD row pitch - 64 lanes that
+// each walk their own row then hit 64 different banks - and every thread takes its row into registers from there.
+// The backward writes its gradient rows the same way in reverse.
+constexpr int HL_CP = 13, HL_RP = 31;   // LDS pitch of a 12- / 30-float row
+
+template <int W, int T>
+__device__ __forceinline__ void tile_load(const float* __restrict__ g, int nrows, float* v) {
+#pragma unroll
+  for (int i = 0; i < W; ++i) {
+    const int e = i * T + (int)threadIdx.x;
+    v[i] = e < nrows * W ? g[e] : 0.f;
+  }
+}
+template <int W, int PITCH, int T>
+__device__ __forceinline__ void tile_to_lds(const float* v, float* s) {
+#pragma unroll
+  for (int i = 0; i < W; ++i) {
+    const int e = i * T + (int)threadIdx.x;
+    s[(e / W) * PITCH + e % W] = v[i];
+  }
+}
+template <int W, int PITCH, int T>
+__device__ __forceinline__ void tile_store(float* __restrict__ g, int nrows, const float* s) {
+#pragma unroll
+  for (int i = 0; i < W; ++i) {
+    const int e = i * T + (int)threadIdx.x;
+    if (e < nrows * W) g[e] = s[(e / W) * PITCH + e % W];
+  }
+}
+
+// one thread per proposal row, 64 rows per wave; the seven sums go over the wave on DPP.  WAVES = 1: one atomic
+// per wave and output - 2 048 rows are 32 workgroups.  WAVES = 4 serves R <= 256 as ONE workgroup whose four
+// wave sums are added in a fixed order, one atomic per output: such a launch stays deterministic.
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void head_loss_fwd_k(
     HeadLossCfg c, const float* __restrict__ cls, const float* __restrict__ reg,
     const float* __restrict__ base, const float* __restrict__ center_t,
     const float* __restrict__ size_t_, const long long* __restrict__ dircls_t,
     const float* __restrict__ dirres_t, const long long* __restrict__ sem_t,
     const long long* __restrict__ obj_t, const float* __restrict__ obj_w,
     const float* __restrict__ box_w, float* __restrict__ out) {
-  __shared__ float red[NLOSS][256];
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  constexpr int T = 64 * WAVES;
+  __shared__ float s_cls[T * HL_CP];
+  __shared__ float s_reg[T * HL_RP];
+  __shared__ float s_part[WAVES][NLOSS + 1];
+  const int tile0 = blockIdx.x * T;
+  const int nrows = c.R - tile0 < T ? c.R - tile0 : T;
+  const int r = tile0 + (int)threadIdx.x;
+  const int rr = r < c.R ? r : c.R - 1;
+  // the row's operands, all loaded up front: no load waits for another one (rr: the row, clamped into [0, R))
+  float wc[12], rg[30], pb[3], ct[3], st[3], w_box, w_obj, rt;
+  int ot, dt, sem;
+  {
+    float vc[12], vr[30];
+    tile_load<12, T>(cls + (size_t)tile0 * 12, nrows, vc);
+    tile_load<30, T>(reg + (size_t)tile0 * 30, nrows, vr);
+    w_box = box_w[rr]; w_obj = obj_w[rr]; rt = dirres_t[rr];
+    ot = (int)obj_t[rr]; dt = (int)dircls_t[rr]; sem = (int)sem_t[rr];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      pb[k] = base[(size_t)rr * 3 + k];
+      ct[k] = center_t[(size_t)rr * 3 + k];
+      st[k] = size_t_[(size_t)rr * 3 + k];
+    }
+    tile_to_lds<12, HL_CP, T>(vc, s_cls);
+    tile_to_lds<30, HL_RP, T>(vr, s_reg);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 12; ++i) wc[i] = s_cls[threadIdx.x * HL_CP + i];
+#pragma unroll
+  for (int i = 0; i < 30; ++i) rg[i] = s_reg[threadIdx.x * HL_RP + i];
+  // the residual at the target direction class: an LDS read at a run-time column (dt is in a register by now), so
+  // the 30-float row keeps compile-time indices alone and stays in registers
+  const float res_dt = s_reg[threadIdx.x * HL_RP + 18 + (dt < 0 ? 0 : (dt > 11 ? 11 : dt))];
   float l[NLOSS] = {0, 0, 0, 0, 0, 0, 0};
   if (r < c.R) {
-    const float* pc = cls + (size_t)r * c.ncls;
-    const float* pr = reg + (size_t)r * c.nreg;
-    const float bw = box_w[r];
-    const int ot = (int)obj_t[r];
-    l[0] = c.w_obj * obj_w[r] * (ot ? c.cw1 : c.cw0) * ce<2>(pc, 2, ot, nullptr, 0.f);
+    const float bw = w_box;
+    l[0] = c.w_obj * w_obj * (ot ? c.cw1 : c.cw0) * ce_reg<2>(wc, ot, nullptr, 0.f);
     if (bw != 0.f) {   // every box term carries the weight objectness_target / n_pos
-      const int dt = (int)dircls_t[r];
       float cen[3], siz[3];
+#pragma unroll
       for (int k = 0; k < 3; ++k) {
-        cen[k] = base[r * 3 + k] + pr[k];
-        siz[k] = pr[3 + k];
+        cen[k] = pb[k] + rg[k];
+        siz[k] = rg[3 + k];
       }
-      l[1] = c.w_dircls * bw * ce<12>(pr + 6, c.nbins, dt, nullptr, 0.f);
-      l[2] = c.w_dirres * bw * smooth_l1(pr[6 + c.nbins + dt] - dirres_t[r], c.beta_dirres);
+      l[1] = c.w_dircls * bw * ce_reg<12>(rg + 6, dt, nullptr, 0.f);
+      l[2] = c.w_dirres * bw * smooth_l1(res_dt - rt, c.beta_dirres);
+#pragma unroll
       for (int k = 0; k < 3; ++k) {
-        l[3] += c.w_size * bw * smooth_l1(siz[k] - size_t_[r * 3 + k], c.beta_size);
-        l[4] += c.w_center * bw * smooth_l1(cen[k] - center_t[r * 3 + k], c.beta_center);
+        l[3] += c.w_size * bw * smooth_l1(siz[k] - st[k], c.beta_size);
+        l[4] += c.w_center * bw * smooth_l1(cen[k] - ct[k], c.beta_center);
       }
-      l[5] = c.w_sem * bw * ce<10>(pc + 2, c.nsem, (int)sem_t[r], nullptr, 0.f);
-      const IoU u = aa_iou(cen, siz, center_t + r * 3, size_t_ + r * 3);
+      l[5] = c.w_sem * bw * ce_reg<10>(wc + 2, sem, nullptr, 0.f);
+      const IoU u = aa_iou(cen, siz, ct, st);
       l[6] = c.w_iou * bw * (1.f - u.iou);
     }
   }
 #pragma unroll
-  for (int i = 0; i < NLOSS; ++i) red[i][threadIdx.x] = l[i];
-  __syncthreads();
-  for (int sft = 128; sft > 0; sft >>= 1) {
-    if (threadIdx.x < sft)
+  for (int i = 0; i < NLOSS; ++i) l[i] = wave_sum(l[i]);
+  const int lane = threadIdx.x & 63;
+  float mine = l[0];                     // lane i < 7 takes sum i
 #pragma unroll
-      for (int i = 0; i < NLOSS; ++i) red[i][threadIdx.x] += red[i][threadIdx.x + sft];
+  for (int i = 1; i < NLOSS; ++i) mine = lane == i ? l[i] : mine;
+  if constexpr (WAVES == 1) {
+    if (lane < NLOSS) atomicAdd(out + lane, mine);
+  } else {
+    if (lane < NLOSS) s_part[threadIdx.x >> 6][lane] = mine;
     __syncthreads();
+    if (threadIdx.x < NLOSS) {
+      float t = s_part[0][threadIdx.x];
+#pragma unroll
+      for (int w = 1; w < WAVES; ++w) t += s_part[w][threadIdx.x];
+      atomicAdd(out + threadIdx.x, t);
+    }
   }
-  if (threadIdx.x < NLOSS) atomicAdd(out + threadIdx.x, red[threadIdx.x][0]);
 }
 
-// gradients wrt cls (R,12), reg (R,30), base (R,3) given the 7 upstream scalars gout[7]
-__global__ __launch_bounds__(256) void head_loss_bwd_k(
+// gradients wrt cls (R,12), reg (R,30), base (R,3) given the 7 upstream scalars gout[7]: one wave per workgroup,
+// one row per lane, the gradient rows in registers and out through the LDS tiles
+__global__ __launch_bounds__(64) void head_loss_bwd_k(
     HeadLossCfg c, const float* __restrict__ cls, const float* __restrict__ reg,
     const float* __restrict__ base, const float* __restrict__ center_t,
     const float* __restrict__ size_t_, const long long* __restrict__ dircls_t,
@@ -134,51 +250,85 @@ __global__ __launch_bounds__(256) void head_loss_bwd_k(
     const long long* __restrict__ obj_t, const float* __restrict__ obj_w,
     const float* __restrict__ box_w, const float* __restrict__ gout,
     float* __restrict__ gcls, float* __restrict__ greg, float* __restrict__ gbase) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= c.R) return;
-  const float* pc = cls + (size_t)r * c.ncls;
-  const float* pr = reg + (size_t)r * c.nreg;
+  constexpr int T = 64;
+  __shared__ float s_cls[T * HL_CP];
+  __shared__ float s_reg[T * HL_RP];
+  const int tile0 = blockIdx.x * T;
+  const int nrows = c.R - tile0 < T ? c.R - tile0 : T;
+  const int r = tile0 + (int)threadIdx.x;
+  const int rr = r < c.R ? r : c.R - 1;
+  // the row's operands, all loaded up front: no load waits for another one (rr: the row, clamped into [0, R))
+  float wc[12], rg[30], pb[3], ct[3], st[3], w_box, w_obj, rt;
+  int ot, dt, sem;
+  {
+    float vc[12], vr[30];
+    tile_load<12, T>(cls + (size_t)tile0 * 12, nrows, vc);
+    tile_load<30, T>(reg + (size_t)tile0 * 30, nrows, vr);
+    w_box = box_w[rr]; w_obj = obj_w[rr]; rt = dirres_t[rr];
+    ot = (int)obj_t[rr]; dt = (int)dircls_t[rr]; sem = (int)sem_t[rr];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      pb[k] = base[(size_t)rr * 3 + k];
+      ct[k] = center_t[(size_t)rr * 3 + k];
+      st[k] = size_t_[(size_t)rr * 3 + k];
+    }
+    tile_to_lds<12, HL_CP, T>(vc, s_cls);
+    tile_to_lds<30, HL_RP, T>(vr, s_reg);
+  }
+  float go[NLOSS];
+#pragma unroll
+  for (int i = 0; i < NLOSS; ++i) go[i] = gout[i];
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 12; ++i) wc[i] = s_cls[threadIdx.x * HL_CP + i];
+#pragma unroll
+  for (int i = 0; i < 30; ++i) rg[i] = s_reg[threadIdx.x * HL_RP + i];
+  // the residual at the target direction class: an LDS read at a run-time column (dt is in a register by now), so
+  // the 30-float row keeps compile-time indices alone and stays in registers
+  const float res_dt = s_reg[threadIdx.x * HL_RP + 18 + (dt < 0 ? 0 : (dt > 11 ? 11 : dt))];
   float gc[12], gr[30];
-  for (int i = 0; i < c.ncls; ++i) gc[i] = 0.f;
-  for (int i = 0; i < c.nreg; ++i) gr[i] = 0.f;
-  const float bw = box_w[r];
-  const int ot = (int)obj_t[r];
-  ce<2>(pc, 2, ot, gc, gout[0] * c.w_obj * obj_w[r] * (ot ? c.cw1 : c.cw0));
+#pragma unroll
+  for (int i = 0; i < 12; ++i) gc[i] = 0.f;
+#pragma unroll
+  for (int i = 0; i < 30; ++i) gr[i] = 0.f;
+  const float bw = w_box;
+  ce_reg<2>(wc, ot, gc, go[0] * c.w_obj * w_obj * (ot ? c.cw1 : c.cw0));
   if (bw != 0.f) {
-    const int dt = (int)dircls_t[r];
     float cen[3], siz[3];
+#pragma unroll
     for (int k = 0; k < 3; ++k) {
-      cen[k] = base[r * 3 + k] + pr[k];
-      siz[k] = pr[3 + k];
+      cen[k] = pb[k] + rg[k];
+      siz[k] = rg[3 + k];
     }
-    ce<12>(pr + 6, c.nbins, dt, gr + 6, gout[1] * c.w_dircls * bw);
-    gr[6 + c.nbins + dt] += gout[2] * c.w_dirres * bw *
-                            smooth_l1_grad(pr[6 + c.nbins + dt] - dirres_t[r], c.beta_dirres);
+    ce_reg<12>(rg + 6, dt, gr + 6, go[1] * c.w_dircls * bw);
+    const float g_res = go[2] * c.w_dirres * bw * smooth_l1_grad(res_dt - rt, c.beta_dirres);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) gr[18 + i] = i == dt ? g_res : 0.f;
+#pragma unroll
     for (int k = 0; k < 3; ++k) {
-      gr[3 + k] += gout[3] * c.w_size * bw * smooth_l1_grad(siz[k] - size_t_[r * 3 + k], c.beta_size);
-      gr[k] += gout[4] * c.w_center * bw * smooth_l1_grad(cen[k] - center_t[r * 3 + k], c.beta_center);
+      gr[3 + k] += go[3] * c.w_size * bw * smooth_l1_grad(siz[k] - st[k], c.beta_size);
+      gr[k] += go[4] * c.w_center * bw * smooth_l1_grad(cen[k] - ct[k], c.beta_center);
     }
-    ce<10>(pc + 2, c.nsem, (int)sem_t[r], gc + 2, gout[5] * c.w_sem * bw);
+    ce_reg<10>(wc + 2, sem, gc + 2, go[5] * c.w_sem * bw);
     // IoU: loss = 1 - ov/u ; d(ov)/d(.) via the intersection extents, d(a1)/d(size)
-    const IoU u = aa_iou(cen, siz, center_t + r * 3, size_t_ + r * 3);
-    const float gl = -gout[6] * c.w_iou * bw;       // d total / d iou
+    const IoU u = aa_iou(cen, siz, ct, st);
+    const float gl = -go[6] * c.w_iou * bw;         // d total / d iou
     // d iou = (d ov * u - ov * d u) / u^2, d u = d a1 - d ov (unless clamped: d u = 0)
     const float inv_u = 1.f / u.uni;
     const float k_ov = gl * (inv_u + (u.clamped ? 0.f : u.overlap * inv_u * inv_u));
     const float k_a1 = u.clamped ? 0.f : -gl * u.overlap * inv_u * inv_u;
-    float ext[3], sz[3];
-    for (int k = 0; k < 3; ++k) {
-      ext[k] = fmaxf(u.hi[k] - u.lo[k], 0.f);
-      sz[k] = siz[k];
-    }
+    float ext[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ext[k] = fmaxf(u.hi[k] - u.lo[k], 0.f);
+#pragma unroll
     for (int k = 0; k < 3; ++k) {
       const float other_ov = ext[(k + 1) % 3] * ext[(k + 2) % 3];
-      const float other_a1 = sz[(k + 1) % 3] * sz[(k + 2) % 3];
+      const float other_a1 = siz[(k + 1) % 3] * siz[(k + 2) % 3];
       float d_hi_c = 0.f, d_hi_s = 0.f, d_lo_c = 0.f, d_lo_s = 0.f;
       if (u.pos[k]) {
         const float l1 = cen[k] - siz[k] * 0.5f, h1 = cen[k] + siz[k] * 0.5f;
-        const float l2 = center_t[r * 3 + k] - size_t_[r * 3 + k] * 0.5f;
-        const float h2 = center_t[r * 3 + k] + size_t_[r * 3 + k] * 0.5f;
+        const float l2 = ct[k] - st[k] * 0.5f;
+        const float h2 = ct[k] + st[k] * 0.5f;
         // torch.min/max backward: on ties the gradient is split evenly between both operands
         const float wh = h1 < h2 ? 1.f : (h1 == h2 ? 0.5f : 0.f);
         const float wl = l1 > l2 ? 1.f : (l1 == l2 ? 0.5f : 0.f);
@@ -192,9 +342,16 @@ __global__ __launch_bounds__(256) void head_loss_bwd_k(
       gr[3 + k] += g_s;
     }
   }
-  for (int i = 0; i < c.ncls; ++i) gcls[(size_t)r * c.ncls + i] = gc[i];
-  for (int i = 0; i < c.nreg; ++i) greg[(size_t)r * c.nreg + i] = gr[i];
-  for (int k = 0; k < 3; ++k) gbase[r * 3 + k] = gr[k];   // centre = base + offset
+  // every lane has read its own LDS row and now overwrites that row alone: no barrier needed before these writes
+#pragma unroll
+  for (int i = 0; i < 12; ++i) s_cls[threadIdx.x * HL_CP + i] = gc[i];
+#pragma unroll
+  for (int i = 0; i < 30; ++i) s_reg[threadIdx.x * HL_RP + i] = gr[i];
+  __syncthreads();
+  tile_store<12, HL_CP, T>(gcls + (size_t)tile0 * 12, nrows, s_cls);
+  tile_store<30, HL_RP, T>(greg + (size_t)tile0 * 30, nrows, s_reg);
+  for (int e = threadIdx.x; e < nrows * 3; e += T)           // centre = base + offset: the same gradient
+    gbase[(size_t)tile0 * 3 + e] = s_reg[(e / 3) * HL_RP + e % 3];
 }
 
 // ---- distance form: CAVoteHead.loss (class_agnostic_vote_head.py:40-121) -----------------------
@@ -231,35 +388,6 @@ __device__ __forceinline__ void ca_load(int r, const float* __restrict__ cls, co
   for (int i = 0; i < 6; ++i) t[i] = fmaxf(pt[i], 0.f);      // distance_targets.clamp_(min=0), :301
 #pragma unroll
   for (int i = 0; i < 6; ++i) d[i] = expf(lg[i]);
-}
-
-// ce<> above on a register array: every index is a compile-time constant after unrolling (the target is
-// picked by selects), so the row never goes to scratch memory; the arithmetic is the same, term by term
-template <int N>
-__device__ __forceinline__ float ce_reg(const float* p, int t, float* grad /*nullable*/, float gscale) {
-  float m = p[0];
-#pragma unroll
-  for (int i = 1; i < N; ++i) m = fmaxf(m, p[i]);
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < N; ++i) s += __expf(p[i] - m);
-  const float lse = m + __logf(s);
-  float pt = p[0];
-#pragma unroll
-  for (int i = 1; i < N; ++i) pt = i == t ? p[i] : pt;
-  if (grad) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) grad[i] += gscale * (__expf(p[i] - lse) - (i == t ? 1.f : 0.f));
-  }
-  return lse - pt;
-}
-
-// v[j] of a 12-element register array, j in 0..11
-__device__ __forceinline__ float pick12(const float* v, int j) {
-  float r = v[0];
-#pragma unroll
-  for (int i = 1; i < 12; ++i) r = i == j ? v[i] : r;
-  return r;
 }
 
 struct CaIoU {
@@ -476,6 +604,69 @@ __global__ __launch_bounds__(256) void vote_loss_k(
   }
 }
 
+// The counting forward for gt_per_seed = 3 (the model's; any other count keeps vote_loss_k<true>).  The positive
+// seeds are counted ONCE per launch: a workgroup looks at its own 256 seeds only - one index -> (mask, nine target
+// floats) chain per thread, vote and seed point fetched beside it - and adds its count and its UNSCALED sum
+// sum_i mask_i * min_j L1_ij to two device words; the last workgroup to arrive (ticket) reads both back, stores the
+// count for the backward and adds sum * w to out, w = 1 / (count + 1e-6) * dst_weight - the weight every positive
+// seed carries in vote_loss_k, applied once to the sum instead of once per |difference| (inside the bound of the edge
+// tests: a few roundings of the total).  Before, each of the B*S / 256 workgroups gathered the masks of all B*S seeds.
+// Ordering as in bn_fin.h: the words are touched by device-scope atomics only and read back with atomicExch, which
+// also leaves them zeroed for the next launch; a workgroup's adds are acknowledged (vmcnt) before it takes its ticket.
+// One launch at a time per device: the words belong to the library, not to the call.
+struct VoteAcc { unsigned ticket; int count; float usum; };
+__device__ VoteAcc g_vote_acc = {0u, 0, 0.f};
+
+__global__ __launch_bounds__(256) void vote_loss_count_fwd_k(
+    int B, int S, int N, float wdst, const float* __restrict__ seed, const float* __restrict__ vote,
+    const long long* __restrict__ seed_idx, const long long* __restrict__ tmask, const float* __restrict__ vtgt,
+    float* __restrict__ out, float* __restrict__ mask_sum_out) {
+  __shared__ int s_cnt[4];
+  __shared__ float s_sum[4];
+  const int total = B * S;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = i < total;
+  const int ii = live ? i : total - 1;
+  const int b = ii / S;
+  const long long k = seed_idx[ii];
+  float vt[3], sd[3], t[9];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    vt[c] = vote[(size_t)ii * 3 + c];
+    sd[c] = seed[(size_t)ii * 3 + c];
+  }
+  const long long m = tmask[(size_t)b * N + k];
+  const float* pt = vtgt + ((size_t)b * N + k) * 9;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) t[q] = pt[q];
+  float best = 3.0e38f;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    float d = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) d += fabsf(vt[c] - (t[j * 3 + c] + sd[c]));
+    if (d < best) best = d;
+  }
+  const float u = wave_sum(live && m != 0 ? (float)m * best : 0.f);
+  const int cnt = wave_sum_i(live ? (int)m : 0);
+  if ((threadIdx.x & 63) == 0) {
+    s_cnt[threadIdx.x >> 6] = cnt;
+    s_sum[threadIdx.x >> 6] = u;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  VoteAcc* acc = &g_vote_acc;
+  atomicAdd(&acc->count, s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3]);
+  atomicAdd(&acc->usum, (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (atomicAdd(&acc->ticket, 1u) != gridDim.x - 1) return;
+  atomicExch(&acc->ticket, 0u);
+  const float msum = (float)atomicExch(&acc->count, 0);
+  const float usum = atomicExch(&acc->usum, 0.f);
+  mask_sum_out[0] = msum;
+  atomicAdd(out, usum * (1.f / (msum + 1e-6f) * wdst));
+}
+
 
 // ---- vote targets (get_targets_single :828-858, batched) ---------------------------------------
 // One thread per point: membership in the (<= 64) ground-truth boxes of its scene, votes towards the
@@ -491,6 +682,7 @@ __global__ __launch_bounds__(256) void vote_targets_k(int N, int pstride, int G,
                                                       float* __restrict__ vt,
                                                       long long* __restrict__ mask) {
   __shared__ float s_box[64 * 8];   // cx, cy, cz(gravity), hx, hy, hz, cos, sin
+  __shared__ float s_vt[256 * 9];   // the workgroup's target rows on their way out
   const int b = blockIdx.y;
   for (int i = threadIdx.x; i < G; i += blockDim.x) {
     const float* g = gt + ((size_t)b * G + i) * 7;
@@ -502,9 +694,10 @@ __global__ __launch_bounds__(256) void vote_targets_k(int N, int pstride, int G,
     o[7] = valid[(size_t)b * G + i] ? sn[(size_t)b * G + i] : __builtin_nanf("");  // NaN = invalid
   }
   __syncthreads();
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
-  const float* p = points + ((size_t)b * N + n) * pstride;
+  const int n0 = blockIdx.x * blockDim.x;
+  const int n = n0 + threadIdx.x;
+  const int nn = n < N ? n : N - 1;                   // a tail thread recomputes the last point and stores nothing
+  const float* p = points + ((size_t)b * N + nn) * pstride;
   const float px = p[0], py = p[1], pz = p[2];
   int total = 0;
   float v1[3] = {0.f, 0.f, 0.f}, v2[3] = {0.f, 0.f, 0.f}, vl[3] = {0.f, 0.f, 0.f};
@@ -522,14 +715,24 @@ __global__ __launch_bounds__(256) void vote_targets_k(int N, int pstride, int G,
       vl[0] = -r0; vl[1] = -r1; vl[2] = -r2;
     }
   }
-  float* o = vt + ((size_t)b * N + n) * 9;
+  // the nine floats of a point go to LDS (pitch 9: odd, conflict-free) and leave as one contiguous run of the
+  // workgroup's points, lane-consecutive dwords, instead of nine stores at a 36-byte stride per lane
+  float* o = s_vt + threadIdx.x * 9;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     o[c] = total > 0 ? v1[c] : 0.f;
     o[3 + c] = total > 0 ? (total >= 2 ? v2[c] : v1[c]) : 0.f;
     o[6 + c] = total > 0 ? (total >= 3 ? vl[c] : v1[c]) : 0.f;
   }
-  mask[(size_t)b * N + n] = total > 0 ? 1 : 0;
+  if (n < N) mask[(size_t)b * N + n] = total > 0 ? 1 : 0;
+  __syncthreads();
+  const int cnt = (N - n0 < 256 ? N - n0 : 256) * 9;
+  float* g = vt + ((size_t)b * N + n0) * 9;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    const int e = q * 256 + (int)threadIdx.x;
+    if (e < cnt) g[e] = s_vt[e];
+  }
 }
 
 
@@ -757,10 +960,17 @@ extern "C" int demf_head_loss_fwd(int R, int num_dir_bins, int num_classes, cons
   if (R == 0) return DEMF_OK;
   DEMF_REQUIRE(hyper12 && cls && reg && base_xyz && center_t && size_t_ && dir_class_t && dir_res_t &&
                    sem_t && obj_t && obj_w && box_w && out7, "head_loss_fwd: null pointer");
-  hipLaunchKernelGGL(head_loss_fwd_k, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream,
-                     make_cfg(R, hyper12), cls, reg, base_xyz, center_t, size_t_,
-                     (const long long*)dir_class_t, dir_res_t, (const long long*)sem_t,
-                     (const long long*)obj_t, obj_w, box_w, out7);
+  // up to 256 rows: one workgroup of four waves, one atomic per output (deterministic); beyond: one wave each
+  if (R <= 256)
+    hipLaunchKernelGGL(head_loss_fwd_k<4>, dim3(1), dim3(256), 0, (hipStream_t)stream,
+                       make_cfg(R, hyper12), cls, reg, base_xyz, center_t, size_t_,
+                       (const long long*)dir_class_t, dir_res_t, (const long long*)sem_t,
+                       (const long long*)obj_t, obj_w, box_w, out7);
+  else
+    hipLaunchKernelGGL(head_loss_fwd_k<1>, dim3(cdiv(R, 64)), dim3(64), 0, (hipStream_t)stream,
+                       make_cfg(R, hyper12), cls, reg, base_xyz, center_t, size_t_,
+                       (const long long*)dir_class_t, dir_res_t, (const long long*)sem_t,
+                       (const long long*)obj_t, obj_w, box_w, out7);
   return check_launch("head_loss_fwd");
 }
 
@@ -777,7 +987,7 @@ extern "C" int demf_head_loss_bwd(int R, int num_dir_bins, int num_classes, cons
   DEMF_REQUIRE(hyper12 && cls && reg && base_xyz && center_t && size_t_ && dir_class_t && dir_res_t &&
                    sem_t && obj_t && obj_w && box_w && grad_out7 && grad_cls && grad_reg && grad_base,
                "head_loss_bwd: null pointer");
-  hipLaunchKernelGGL(head_loss_bwd_k, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(head_loss_bwd_k, dim3(cdiv(R, 64)), dim3(64), 0, (hipStream_t)stream,
                      make_cfg(R, hyper12), cls, reg, base_xyz, center_t, size_t_,
                      (const long long*)dir_class_t, dir_res_t, (const long long*)sem_t,
                      (const long long*)obj_t, obj_w, box_w, grad_out7, grad_cls, grad_reg, grad_base);
@@ -812,11 +1022,16 @@ extern "C" int demf_vote_loss_fwd(int B, int S, int N, int gt_per_seed, float ds
   if (B * S == 0) return DEMF_OK;
   DEMF_REQUIRE(seed_points && vote_points && seed_indices && vote_target_masks && vote_targets,
                "vote_loss_fwd: null pointer");
-  hipLaunchKernelGGL(vote_loss_k<true>, dim3(cdiv(B * S, 256)), dim3(256), 0, (hipStream_t)stream, B, S, N,
-                     3 * gt_per_seed, dst_weight, seed_points, vote_points,
-                     (const long long*)seed_indices, (const long long*)vote_target_masks,
-                     vote_targets, (const float*)nullptr, (const float*)nullptr, out, (float*)nullptr,
-                     mask_sum_out);
+  if (gt_per_seed == 3)
+    hipLaunchKernelGGL(vote_loss_count_fwd_k, dim3(cdiv(B * S, 256)), dim3(256), 0, (hipStream_t)stream, B, S, N,
+                       dst_weight, seed_points, vote_points, (const long long*)seed_indices,
+                       (const long long*)vote_target_masks, vote_targets, out, mask_sum_out);
+  else
+    hipLaunchKernelGGL(vote_loss_k<true>, dim3(cdiv(B * S, 256)), dim3(256), 0, (hipStream_t)stream, B, S, N,
+                       3 * gt_per_seed, dst_weight, seed_points, vote_points,
+                       (const long long*)seed_indices, (const long long*)vote_target_masks,
+                       vote_targets, (const float*)nullptr, (const float*)nullptr, out, (float*)nullptr,
+                       mask_sum_out);
   return check_launch("vote_loss_fwd");
 }
 

@@ -161,6 +161,17 @@ __global__ __launch_bounds__(256) void sumsq_k(long long n, const float* __restr
   block_add_sumsq(acc, st);
 }
 
+// One element of the update, the expression of torch.optim.AdamW term for term (every path of adamw_state_k
+// goes through it, so a float4 lane and a peeled element give the same bits).
+__device__ __forceinline__ void adamw_one(float& p, float g_in, float& m, float& v, float coef, float decay,
+                                          float step, float beta1, float beta2, float bias_c2_sqrt, float eps) {
+  const float g = g_in * coef;
+  p *= decay;
+  m = beta1 * m + (1.f - beta1) * g;
+  v = beta2 * v + (1.f - beta2) * g * g;
+  p -= step * (m / (sqrtf(v) / bias_c2_sqrt + eps));
+}
+
 struct AdamWSeg {
   long long start, n;
   float lr, weight_decay;
@@ -178,6 +189,10 @@ struct AdamWStateArgs {
   float max_norm, grad_scale, beta1, beta2, eps;
 };
 
+// first-level ticket words of adamw_state_k (see its end): zero between launches; one launch at a time per device
+constexpr unsigned TK_GROUPS = 32, TK_PITCH = 32;
+__device__ unsigned g_adamw_tickets[TK_GROUPS * TK_PITCH];
+
 // Every parameter group in ONE launch.  t = st->t + 1; clip coefficient from st->sumsq; the last
 // workgroup to finish (ticket) publishes t, clears sumsq and the ticket for the next step.
 __global__ __launch_bounds__(256) void adamw_state_k(AdamWStateArgs a) {
@@ -187,6 +202,31 @@ __global__ __launch_bounds__(256) void adamw_state_k(AdamWStateArgs a) {
   for (int k = 1; k < a.nseg; ++k)
     if (blockIdx.x >= a.seg[k].block0) s = k;
   const AdamWSeg sg = a.seg[s];
+  const unsigned nblk = (s + 1 < a.nseg ? a.seg[s + 1].block0 : gridDim.x) - sg.block0;
+  const long long stride = (long long)nblk * blockDim.x * 4;
+  float* P = a.p + sg.start;
+  const float* G = a.g + sg.start;
+  float* M = a.m + sg.start;
+  float* V = a.v + sg.start;
+  // float4 body whenever the four pointers share one residue mod 16 bytes: up to three leading elements are
+  // peeled (by the segment's first thread) so that the body starts on a 16-byte boundary of all four.  The
+  // decoder group starts at an odd element of the flat buffers; without the peel it ran the scalar branch whole.
+  const size_t res = (size_t)P & 15;
+  const bool vec = (res & 3) == 0 && ((size_t)G & 15) == res && ((size_t)M & 15) == res && ((size_t)V & 15) == res;
+  long long lead = vec ? (long long)(((16 - res) & 15) >> 2) : 0;
+  if (lead > sg.n) lead = sg.n;
+  const long long tid = (long long)(blockIdx.x - sg.block0) * blockDim.x + threadIdx.x;
+  // The first float4s are requested BEFORE the step's scalars exist: thread 0's chain (state load, two fp64 pow,
+  // sqrt) then runs under the memory latency of the whole workgroup instead of in front of it.
+  long long i = lead + tid * 4;
+  float4 p = make_float4(0.f, 0.f, 0.f, 0.f), g4 = p, m = p, v = p;
+  bool loaded = vec && i + 4 <= sg.n;
+  if (loaded) {
+    p = *reinterpret_cast<float4*>(P + i);
+    g4 = *reinterpret_cast<const float4*>(G + i);
+    m = *reinterpret_cast<float4*>(M + i);
+    v = *reinterpret_cast<float4*>(V + i);
+  }
   if (threadIdx.x == 0) {
     const long long t = st->t + 1;
     const float lr = sg.lr * st->lr_factor;
@@ -203,50 +243,49 @@ __global__ __launch_bounds__(256) void adamw_state_k(AdamWStateArgs a) {
   }
   __syncthreads();
   const float coef = sh[0], decay = sh[1], step = sh[2], bias_c2_sqrt = sh[3];
-  const unsigned nblk = (s + 1 < a.nseg ? a.seg[s + 1].block0 : gridDim.x) - sg.block0;
-  const long long stride = (long long)nblk * blockDim.x * 4;
-  float* P = a.p + sg.start;
-  const float* G = a.g + sg.start;
-  float* M = a.m + sg.start;
-  float* V = a.v + sg.start;
-  const bool vec = (((size_t)P | (size_t)G | (size_t)M | (size_t)V) & 15) == 0;
-  for (long long i = ((long long)(blockIdx.x - sg.block0) * blockDim.x + threadIdx.x) * 4; i < sg.n; i += stride) {
+  if (tid == 0)
+    for (long long j = 0; j < lead; ++j)
+      adamw_one(P[j], G[j], M[j], V[j], coef, decay, step, a.beta1, a.beta2, bias_c2_sqrt, a.eps);
+  for (; i < sg.n; i += stride) {
     if (vec && i + 4 <= sg.n) {
-      float4 p = *reinterpret_cast<float4*>(P + i);
-      const float4 g4 = *reinterpret_cast<const float4*>(G + i);
-      float4 m = *reinterpret_cast<float4*>(M + i);
-      float4 v = *reinterpret_cast<float4*>(V + i);
-      float* pp = &p.x; const float* gg = &g4.x; float* mm = &m.x; float* vv = &v.x;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float g = gg[k] * coef;
-        pp[k] *= decay;
-        mm[k] = a.beta1 * mm[k] + (1.f - a.beta1) * g;
-        vv[k] = a.beta2 * vv[k] + (1.f - a.beta2) * g * g;
-        pp[k] -= step * (mm[k] / (sqrtf(vv[k]) / bias_c2_sqrt + a.eps));
+      if (!loaded) {
+        p = *reinterpret_cast<float4*>(P + i);
+        g4 = *reinterpret_cast<const float4*>(G + i);
+        m = *reinterpret_cast<float4*>(M + i);
+        v = *reinterpret_cast<float4*>(V + i);
       }
+      loaded = false;
+      adamw_one(p.x, g4.x, m.x, v.x, coef, decay, step, a.beta1, a.beta2, bias_c2_sqrt, a.eps);
+      adamw_one(p.y, g4.y, m.y, v.y, coef, decay, step, a.beta1, a.beta2, bias_c2_sqrt, a.eps);
+      adamw_one(p.z, g4.z, m.z, v.z, coef, decay, step, a.beta1, a.beta2, bias_c2_sqrt, a.eps);
+      adamw_one(p.w, g4.w, m.w, v.w, coef, decay, step, a.beta1, a.beta2, bias_c2_sqrt, a.eps);
       *reinterpret_cast<float4*>(P + i) = p;
       *reinterpret_cast<float4*>(M + i) = m;
       *reinterpret_cast<float4*>(V + i) = v;
     } else {
-      for (long long j = i; j < sg.n && j < i + 4; ++j) {
-        const float g = G[j] * coef;
-        float p = P[j] * decay;
-        const float m = a.beta1 * M[j] + (1.f - a.beta1) * g;
-        const float v = a.beta2 * V[j] + (1.f - a.beta2) * g * g;
-        p -= step * (m / (sqrtf(v) / bias_c2_sqrt + a.eps));
-        P[j] = p; M[j] = m; V[j] = v;
-      }
+      for (long long j = i; j < sg.n && j < i + 4; ++j)
+        adamw_one(P[j], G[j], M[j], V[j], coef, decay, step, a.beta1, a.beta2, bias_c2_sqrt, a.eps);
     }
   }
   __syncthreads();
   if (threadIdx.x == 0) {
     // every workgroup read t / sumsq before it took its ticket: the last one may overwrite them
-    const unsigned ticket = atomicAdd(&st->ticket, 1u);
-    if (ticket == gridDim.x - 1) {
-      st->t = st->t + 1;
-      st->sumsq = 0.0;
-      st->ticket = 0u;
+    // Two levels: a returning atomic on ONE word is served at about 20 ns apiece at its memory channel, and the
+    // 2 039 workgroups of the full model queued up there for longer than the update itself takes (the launch read
+    // 33 us for 61 MB).  Workgroup w first counts into word w % 32 of a library-owned set (one 128-byte line each,
+    // left zeroed by its last member); only the 32 last members go on to the state's ticket.
+    const unsigned total = gridDim.x;
+    const unsigned ngroups = total < TK_GROUPS ? total : TK_GROUPS;
+    const unsigned grp = blockIdx.x % TK_GROUPS;
+    const unsigned members = total / TK_GROUPS + (grp < total % TK_GROUPS ? 1u : 0u);
+    unsigned* sub = g_adamw_tickets + grp * TK_PITCH;
+    if (atomicAdd(sub, 1u) == members - 1) {
+      atomicExch(sub, 0u);
+      if (atomicAdd(&st->ticket, 1u) == ngroups - 1) {
+        st->t = st->t + 1;
+        st->sumsq = 0.0;
+        st->ticket = 0u;
+      }
     }
   }
 }
