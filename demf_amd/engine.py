@@ -102,7 +102,7 @@ class FlatGrads:
         self.flat = torch.zeros(n, dtype=dt, device=dev)
         self.views = []
         self._pending_tables, self._tables = [], []     # address tables of captured pack launches
-        self.captured_pack = False      # set by Trainer.capture around its captures (it calls finish_capture)
+        self.captured_pack = False      # set inside ``capturing`` (Trainer.capture, which calls finish_capture)
         self.sumsq_state = None         # FlatAdamW.state while a capture wants the pack to take the clip norm
         self.mode = None                # gradient accumulation (Trainer(accumulate > 1)): "accumulate" / "last" - the
         #                                 pack ADDS into the buffer; None: it overwrites (one pass per optimizer step)
@@ -180,6 +180,16 @@ class FlatGrads:
         dst = [v for v, g in zip(self.views, grads) if g is not None]
         if dst:
             torch._foreach_add_(dst, [g for g in grads if g is not None])
+
+    @contextlib.contextmanager
+    def capturing(self, mode, sumsq_state):
+        """Around a stream capture of a backward: the pack is ONE launch over an address table, in ``mode``, and
+        takes the clip norm into ``sumsq_state`` (or ``None``); all three are cleared however the capture ends."""
+        self.captured_pack, self.mode, self.sumsq_state = True, mode, sumsq_state
+        try:
+            yield
+        finally:
+            self.captured_pack, self.mode, self.sumsq_state = False, None, None
 
     def reserve_table(self):
         """Room for the address table of one captured pack launch, from the ordinary allocator."""
@@ -337,6 +347,48 @@ def _gc_paused():
             gc.enable()
 
 
+# Replay orders that measured slower than the default and were taken out; ``Trainer.capture`` refuses their
+# switches instead of silently measuring the default order under their name (DESIGN_LOG section 5).
+RETIRED_ORDERS = {
+    "DEMF_GEO_AT_BWD": "forward and backward as two graphs with the pre-pass launched in between measured 6.49 "
+                       "against 6.39 ms per step, later 4.95 against 4.88 ms",
+    "DEMF_GEO_TWO_DEEP": "the pre-pass two steps ahead measured 7.80 against 7.67 ms per step",
+}
+_OVERLAP_REFUSAL = "the overlapped (deferred) update is not available with accumulate = %d > 1: unset " \
+                   "DEMF_AR_OVERLAP / allreduce_overlap"
+
+
+def _capture_plan(accumulate, micro, role, dry, update_in_graph, fused, world, stub, overlap, graph_update,
+                  graph_allreduce, retired_set):
+    """What ``Trainer.capture`` decides before it touches anything -> (role, dry, update_in_graph), or a refusal.
+    No torch and no environment in here: ``overlap`` is ``allreduce_config()[2]``, ``graph_update`` /
+    ``graph_allreduce`` are the values of DEMF_GRAPH_UPDATE / DEMF_GRAPH_ALLREDUCE and ``retired_set`` holds the
+    names of RETIRED_ORDERS found in the environment.  In this order: a retired switch is refused whatever else
+    was asked; with accumulate = 1 the role is ``None`` (asked as ``None`` or "last"); with W > 1 it defaults from
+    ``micro``, the warm-up is dry and the overlapped update is refused; the update goes into the graph only on the
+    fused path, without an all-reduce stub, and on one rank unless the collective is captured too."""
+    if retired_set:
+        name = min(retired_set)
+        raise RuntimeError("%s is set, and the replay order it selected was retired (%s): capture() records the "
+                           "default order only; unset it" % (name, RETIRED_ORDERS[name]))
+    if accumulate == 1:
+        if role not in (None, "last"):
+            raise ValueError("capture(role=%r): with accumulate = 1 every step is the last of its group" % (role,))
+        role = None
+    else:
+        if role is None:
+            role = "last" if micro == accumulate - 1 else "accumulate"
+        if role not in ("accumulate", "last"):
+            raise ValueError("capture(role=%r): 'accumulate' or 'last'" % (role,))
+        if fused and overlap:
+            raise RuntimeError(_OVERLAP_REFUSAL % accumulate)
+        dry = True
+    if update_in_graph is None:
+        update_in_graph = bool(graph_update)
+    update_in_graph = bool(update_in_graph) and fused and stub == 0 and (world == 1 or bool(graph_allreduce))
+    return role, dry, update_in_graph
+
+
 class Trainer:
     """fwd -> loss -> bwd -> one all-reduce -> clip -> AdamW, as one callable step."""
 
@@ -359,6 +411,13 @@ class Trainer:
         self.meter = None
         self._loss_scalars = None          # with a meter: the loss dict's device scalars of the last forward
         self._pending_scalars = None       # ... of the step whose deferred update is still owed
+        self._pending_update = False       # an overlapped step's norm + AdamW are still owed (flush)
+        self.side_stream = None            # the pre-pass stream of the next capture (default: a probed concurrent one)
+        self._comm_stream = None           # the collective's stream, made on first use
+        self.allreduce_stub_us = 0         # > 0: a spin kernel of that length in the collective's place
+        self.allreduce_overlap = None      # None: DEMF_AR_OVERLAP decides
+        self.allreduce_events = None       # a list: HIP event pairs around every collective are appended (bench.py)
+        self._graph = None                 # the hipGraph of the last capture
         groups = model.param_groups(lr=lr, weight_decay=weight_decay)
         self.flat = FlatGrads([p for g in groups for p in g["params"]])
         self.max_grad_norm = max_grad_norm
@@ -432,8 +491,7 @@ class Trainer:
 
     def _refuse_overlap(self):
         if self._accumulate > 1 and self.fused and self.allreduce_config()[2]:
-            raise RuntimeError("the overlapped (deferred) update is not available with accumulate = %d > 1: unset "
-                               "DEMF_AR_OVERLAP / allreduce_overlap" % self._accumulate)
+            raise RuntimeError(_OVERLAP_REFUSAL % self._accumulate)
 
     def _clear_group(self):
         """The clears of a group's last micro-step, behind the AdamW launch that consumed the buffers (kernel
@@ -560,7 +618,7 @@ class Trainer:
     # underneath whatever the caller enqueues in between.  The RCCL call itself stays an ordinary eager call on a
     # stream - nothing is captured, so the multi-GPU path is the one the gloo / shared-GPU tests exercise.
     def _comm(self):
-        if getattr(self, "_comm_stream", None) is None:
+        if self._comm_stream is None:
             self._comm_stream = concurrent_stream()
         return self._comm_stream
 
@@ -569,8 +627,8 @@ class Trainer:
         (bench.py --allreduce-stub-us: the overlap measured on one GPU); overlap is opt-in (DEMF_AR_OVERLAP=1 or
         ``trainer.allreduce_overlap = True``)."""
         world = dist.get_world_size() if dist.is_initialized() else 1
-        stub = int(getattr(self, "allreduce_stub_us", 0) or 0)
-        ov = getattr(self, "allreduce_overlap", None)
+        stub = int(self.allreduce_stub_us or 0)
+        ov = self.allreduce_overlap
         if ov is None:
             # default OFF: measured on MI355X / ROCm 7.2 with a spin kernel in the collective's place
             # (bench.py secondary.allreduce_stub100us_*; profiles/r05_allreduce_overlap_probe.log) the extra
@@ -580,7 +638,7 @@ class Trainer:
         return world, stub, bool(ov) and (world > 1 or stub > 0)
 
     def _collective(self, world, stub):
-        ev = getattr(self, "allreduce_events", None)   # bench.py: HIP events around the collective
+        ev = self.allreduce_events                     # bench.py: HIP events around the collective
         if ev is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -606,7 +664,7 @@ class Trainer:
             self.opt.step(self.max_grad_norm, 1.0 / world, norm_taken=norm_taken)
             return
         # metered: ``scalars`` are the loss tensors of the step this update belongs to - a captured step's own
-        # (its replay closure owns them), else those of the last forward
+        # (its CapturedStep owns them), else those of the last forward
         self.opt.step(self.max_grad_norm, 1.0 / world, norm_taken=norm_taken, meter=self.meter,
                       scalars=self._loss_scalars if scalars is None else scalars)
 
@@ -622,7 +680,7 @@ class Trainer:
     def flush(self):
         """Enqueue the update a deferred (overlapped) step still owes: call before reading parameters,
         gradients or optimizer state.  ``replay()``, ``step()`` and ``state_dict()`` do it themselves."""
-        if getattr(self, "_pending_update", False):
+        if self._pending_update:
             self._pending_update = False
             torch.cuda.current_stream().wait_stream(self._comm())
             scalars, self._pending_scalars = self._pending_scalars, None
@@ -734,45 +792,40 @@ class Trainer:
 
     def capture(self, batch, warmup=3, prefetch_geometry=True, max_gt=None, dry=False, geo_pipe=None,
                 update_in_graph=None, role=None):
-        """Capture forward + loss + backward of ``batch`` (static shapes, device-resident
-        inputs) into one hipGraph; returns ``replay(next_points=None)`` = graph launch + eager
-        all-reduce / clip / AdamW.  The path issues no host sync or host->device copy after
-        warm-up (targets are batched, metas are cached), which is what makes it capturable; the
-        collective and the optimizer stay outside the graph.
+        """Capture forward + loss + backward of ``batch`` (static shapes, device-resident inputs) into one
+        hipGraph; returns a ``CapturedStep``: ``replay(next_points=None)`` = graph launch (+ the eager all-reduce /
+        clip / AdamW where the update is not in the graph).  The path issues no host sync or host->device copy
+        after warm-up (targets are batched, metas are cached), which is what makes it capturable.
 
-        The graph reads STATIC input buffers owned by the returned object: ``replay.load(batch)``
-        copies another batch (same shapes; at most ``max_gt`` boxes per scene, default the
-        largest count in the captured batch) into them and refreshes the cached per-image
-        constants in place, so a training loop is
+        The graph reads STATIC input buffers owned by the returned object: ``replay.load(batch)`` copies another
+        batch (same shapes; at most ``max_gt`` boxes per scene, default the largest count in the captured batch)
+        into them and refreshes the cached per-image constants in place, so a training loop is
 
             replay = trainer.capture(batch_0)
             for k in range(steps):
                 if k: replay.load(batch_k)
                 loss = replay(next_points=batch_{k+1}["points"])
 
-        Batches whose SHAPES differ (padded image size, point count, batch size) need their own
-        graph: ``Trainer.bucketed()`` keeps one per shape.
+        Batches whose SHAPES differ (padded image size, point count, batch size) need their own graph:
+        ``Trainer.bucketed()`` keeps one per shape.
 
-        ``prefetch_geometry``: the coordinate-only pre-pass of the NEXT batch (every FPS level,
-        the backbone ball queries, 3-NN - ``DeMFHotPath.index_geometry``) is issued on a side
-        HIP stream in front of the current batch's fwd+bwd graph, so the latency-bound FPS chain
-        (B workgroups on 256 CUs) runs underneath the current step's forward instead of in front
-        of the next step (``DEMF_GEO_AT_BWD=1``: between a forward and a backward graph).  Every step still computes one full
-        pre-pass; the graph reads it from static buffers that are refreshed by ONE ~6 MB multi-copy
-        launch at the step boundary.
-
-        ``dry``: the warm-up passes run forward + backward only (no optimizer update) and the state
-        they touch (BatchNorm running statistics, dropout counter) is restored afterwards - a capture
-        in the middle of training leaves the model exactly as it found it.
-        ``geo_pipe``: the pre-pass pipeline (``replay.geo``) of another capture with the same cloud
-        shape (B, N, channels): both graphs then read the same index buffers and share one
-        pipelined pre-pass.
-        ``update_in_graph`` (default: on one rank, ``DEMF_GRAPH_UPDATE=0`` turns it off): gradient norm
-        (taken by the gradient pack on its way), clip and AdamW are nodes of the graph too - the
-        optimizer's step count / learning-rate factor / norm live on the device (FlatAdamW.state), so a
-        replay is the WHOLE step and nothing eager follows it.  With more than one rank the collective
-        sits between backward and update and stays an eager RCCL call (``DEMF_GRAPH_ALLREDUCE=1``:
-        captured as well, where the runtime allows it).
+        ``prefetch_geometry``: the coordinate-only pre-pass of the NEXT batch (every FPS level, the backbone ball
+        queries, 3-NN - ``DeMFHotPath.index_geometry``) is issued on a side HIP stream in front of the current
+        batch's graph, so the latency-bound FPS chain (B workgroups on 256 CUs) runs underneath the current step's
+        forward instead of in front of the next step.  Every step still computes one full pre-pass; the graph reads
+        it from static buffers that are refreshed by ONE ~6 MB multi-copy launch at the step boundary.  This is the
+        only replay order: two slower ones (``DEMF_GEO_AT_BWD``, ``DEMF_GEO_TWO_DEEP``) were retired and are
+        refused here, their figures are in DESIGN_LOG section 5.
+        ``dry``: the warm-up passes run forward + backward only (no optimizer update) and the state they touch
+        (BatchNorm running statistics, dropout counter) is restored afterwards - a capture in the middle of
+        training leaves the model exactly as it found it.
+        ``geo_pipe``: the pre-pass pipeline (``replay.geo``) of another capture with the same cloud shape
+        (B, N, channels): both graphs then read the same index buffers and share one pipelined pre-pass.
+        ``update_in_graph`` (default: on one rank, ``DEMF_GRAPH_UPDATE=0`` turns it off): gradient norm (taken by
+        the gradient pack on its way), clip and AdamW are nodes of the graph too - the optimizer's step count /
+        learning-rate factor / norm live on the device (FlatAdamW.state), so a replay is the WHOLE step and nothing
+        eager follows it.  With more than one rank the collective sits between backward and update and stays an
+        eager RCCL call (``DEMF_GRAPH_ALLREDUCE=1``: captured as well, where the runtime allows it).
         ``role`` (``accumulate`` > 1 only; default: from ``trainer.micro``): ``"accumulate"`` - the graph of a
         micro-step 0 .. W-2: forward + backward + ONE demf_multi_add pack (+ one demf_scalars_accum node with a
         meter); ``"last"`` - the graph of micro-step W-1: forward + backward + demf_multi_add_sumsq,
@@ -781,61 +834,45 @@ class Trainer:
         ``"last"`` replay only.  A replay refuses to run when its role does not match ``trainer.micro`` or when
         ``accumulate`` has changed since the capture, and advances ``micro``.  Warm-up passes are always ``dry``
         with W > 1: they must not touch the open group."""
-        dev = batch["points"].device
-        W_c = self._accumulate
-        if W_c == 1:
-            if role not in (None, "last"):
-                raise ValueError("capture(role=%r): with accumulate = 1 every step is the last of its group" % (role,))
-            role = None
-        else:
-            if role is None:
-                role = "last" if self.micro == W_c - 1 else "accumulate"
-            if role not in ("accumulate", "last"):
-                raise ValueError("capture(role=%r): 'accumulate' or 'last'" % (role,))
-            if switches.env_on("DEMF_GEO_AT_BWD"):
-                raise RuntimeError("DEMF_GEO_AT_BWD=1 (forward and backward as two graphs) is not available with "
-                                   "accumulate = %d > 1" % W_c)
-            self._refuse_overlap()
+        world, stub, overlap = self.allreduce_config()
+        role, dry, update_in_graph = _capture_plan(
+            self._accumulate, self.micro, role, dry, update_in_graph, self.fused, world, stub, overlap,
+            switches.env_int("DEMF_GRAPH_UPDATE"), switches.env_int("DEMF_GRAPH_ALLREDUCE"),
+            {name for name in RETIRED_ORDERS if switches.env_on(name)})
+        if role is not None:
             self._ensure_acc()
-            dry = True
-        world_c, stub_c, _ = self.allreduce_config()
-        if update_in_graph is None:
-            update_in_graph = bool(switches.env_int("DEMF_GRAPH_UPDATE"))
-        update_in_graph = bool(update_in_graph) and self.fused and stub_c == 0 and \
-            (world_c == 1 or bool(switches.env_int("DEMF_GRAPH_ALLREDUCE")))
-        gt_list = isinstance(batch["gt_bboxes_3d"], (list, tuple))
-        if gt_list and dev.type == "cuda":
-            G = max_gt or max(1, max(int((b.tensor if hasattr(b, "tensor") else b).shape[0])
-                                     for b in batch["gt_bboxes_3d"]))
-            gt, lab = self.pad_targets(batch["gt_bboxes_3d"], batch["gt_labels_3d"], G, dev)
-        else:
-            G, gt, lab = None, batch["gt_bboxes_3d"], batch["gt_labels_3d"]
-        feats = batch.get("img_features")            # None: a points-only batch - every image block below is skipped
-        head = getattr(self.model, "pts_bbox_head", None) if feats is not None else None
-        # A pyramid handed over as the reference's list of (B,C,H_l,W_l) maps: the captured step reads TOKENS
-        # (channels-last rows, padding zeroed) from a static buffer, and ``load`` converts every new batch
-        # straight out of the caller's maps into that buffer (one tiled-transpose launch) - instead of copying
-        # the 152 MB pyramid into static maps and transposing those inside the graph.
-        tok_static = None
-        if (feats is not None and not isinstance(feats, dict) and dev.type == "cuda" and hasattr(head, "pyramid_tokens")
-                and switches.env_int("DEMF_ZERO_COPY_TOKENS")):
-            tok_static = head.pyramid_tokens(feats, batch["img_metas"])
-        if feats is None:
-            static = dict(points=batch["points"].clone(), gt_bboxes_3d=gt, gt_labels_3d=lab)
-        else:
-            static = dict(points=batch["points"].clone(),
-                          img_features=(tok_static if tok_static is not None else
-                                        dict(feats, tokens=feats["tokens"].clone())
-                                        if isinstance(feats, dict) else [f.clone() for f in feats]),
-                          img_metas=batch["img_metas"], gt_bboxes_3d=gt, gt_labels_3d=lab)
-        batch = static
-        if head is not None and hasattr(head, "pin_metas"):
-            head.pin_metas(static["img_metas"])     # the graph holds raw pointers into its cache entry
-        side = self.side_stream if getattr(self, "side_stream", None) is not None else \
+        step = CapturedStep(self, batch, max_gt, role, update_in_graph, world)
+        dev = batch["points"].device
+        side = self.side_stream if self.side_stream is not None else \
             (concurrent_stream() if dev.type == "cuda" else torch.cuda.Stream())
         if geo_pipe is not None:
             side = geo_pipe.side
         restore = self._snapshot_state() if dry else None
+        self._warm_up(step.static, warmup, dry, role, side)
+        if prefetch_geometry and hasattr(self.model, "index_geometry"):
+            step.geo = self._geo_pipe(step.static["points"], geo_pipe, side)
+        torch.cuda.synchronize()
+        try:
+            self._record(step)
+        except Exception:
+            if restore is not None and role is not None:
+                restore()                 # (the warm-up passes added into the open group)
+            if update_in_graph and world > 1:
+                # the runtime refused to capture the collective: fall back to the eager update
+                # (a second capture: the failed one left nothing behind)
+                return self.capture(step.static, warmup=0, prefetch_geometry=prefetch_geometry, max_gt=max_gt,
+                                    dry=dry, geo_pipe=step.geo if step.geo is not None else geo_pipe,
+                                    update_in_graph=False, role=role)
+            raise
+        self.flat.finish_capture()
+        if restore is not None:
+            restore()
+            torch.cuda.synchronize()
+        self._graph = step.graph
+        return step
+
+    def _warm_up(self, batch, warmup, dry, role, side):
+        """``warmup`` passes over the static inputs on the side stream: real steps, or forward + backward only."""
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             self.flat.mode = role
@@ -849,233 +886,36 @@ class Trainer:
                 self.flat.mode = None
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        can_prefetch = prefetch_geometry and hasattr(self.model, "index_geometry")
-        geo = None
-        if can_prefetch:
-            if geo_pipe is not None:
-                if tuple(geo_pipe.static_pts.shape) != tuple(batch["points"].shape):
-                    raise ValueError("geo_pipe was built for clouds of shape %s, this batch has %s"
-                                     % (tuple(geo_pipe.static_pts.shape), tuple(batch["points"].shape)))
-                geo = geo_pipe
-                # the shared index buffers must describe THIS batch's cloud while it is being captured
-                # (values do not matter to a capture, but the eager bookkeeping below assumes them)
-                geo.ensure(torch.cuda.current_stream(), batch["points"], static["points"])
-            else:
-                geo = _GeoPipe(self.model, batch["points"], side)
-        static_geo = geo.static_geo if geo is not None else None
-        torch.cuda.synchronize()
+
+    def _geo_pipe(self, points, geo_pipe, side):
+        """The pre-pass pipeline of the static cloud ``points``: a new one, or ``geo_pipe`` adopted."""
+        if geo_pipe is None:
+            return _GeoPipe(self.model, points, side)
+        if tuple(geo_pipe.static_pts.shape) != tuple(points.shape):
+            raise ValueError("geo_pipe was built for clouds of shape %s, this batch has %s"
+                             % (tuple(geo_pipe.static_pts.shape), tuple(points.shape)))
+        # the shared index buffers must describe THIS batch's cloud while it is being captured
+        # (values do not matter to a capture, but the eager bookkeeping of the replays assumes them)
+        geo_pipe.ensure(torch.cuda.current_stream(), points, points)
+        return geo_pipe
+
+    def _record(self, step):
+        """Forward + loss + backward of ``step``'s static inputs, and the update where it belongs to the graph,
+        as ONE hipGraph."""
+        in_graph = step.update_in_graph and step.role != "accumulate"
         self.flat.reserve_table()
-        graph = torch.cuda.CUDAGraph()
-        graph_bwd = None
-        if can_prefetch and switches.env_on("DEMF_GEO_AT_BWD"):
-            # DEMF_GEO_AT_BWD=1: forward and backward as two graphs (one memory pool) with the pre-pass
-            # started in between, underneath the backward (round 2's default: 9.26 -> 9.11 ms/step then).
-            # With the one-pass backward kernels of round 3 the backward is ~230 mostly small launches and
-            # every launch pays ~2 us more while a second hardware queue is active, so the pre-pass now
-            # goes underneath the FORWARD (~110 launches) in front of a single fwd+bwd graph:
-            # 6.49 -> 6.39 ms/step.
-            self.flat.captured_pack = True
-            self.flat.sumsq_state = self.opt.state if (update_in_graph and world_c == 1) else None
-            try:
-                with _gc_paused(), torch.cuda.graph(graph):
-                    self._arena(True)            # the arena's single fill is the graph's first node
-                    total = self._fwd(batch, static_geo)
-                graph_bwd = torch.cuda.CUDAGraph()
-                with _gc_paused(), torch.cuda.graph(graph_bwd, pool=graph.pool()):
-                    self.flat.backward_into(total)
-                    if update_in_graph:
-                        self._captured_update(world_c)
-            finally:
-                self._arena(False)
-                self.flat.captured_pack = False
-                self.flat.sumsq_state = None
-            loss = total.detach()
-        else:
-            self.flat.captured_pack = True
-            self.flat.mode = role
-            self.flat.sumsq_state = self.opt.state if (update_in_graph and world_c == 1
-                                                       and role != "accumulate") else None
-            try:
-                with _gc_paused(), torch.cuda.graph(graph):
-                    loss = self._fwd_bwd(batch, static_geo)
-                    if role is not None:
-                        self._accumulate_scalars()
-                    if update_in_graph and role != "accumulate":
-                        self._captured_update(world_c)
-            except Exception:
-                if update_in_graph and world_c > 1:
-                    # the runtime refused to capture the collective: fall back to the eager update
-                    # (a second capture: the failed one left nothing behind)
-                    self.flat.captured_pack = False
-                    self.flat.sumsq_state = None
-                    self.flat.mode = None
-                    if restore is not None and role is not None:
-                        restore()                 # (the warm-up passes added into the open group)
-                    return self.capture(static, warmup=0, prefetch_geometry=prefetch_geometry, max_gt=max_gt,
-                                        dry=dry, geo_pipe=geo if geo is not None else geo_pipe,
-                                        update_in_graph=False, role=role)
-                if restore is not None and role is not None:
-                    restore()
-                raise
-            finally:
-                self.flat.captured_pack = False
-                self.flat.sumsq_state = None
-                self.flat.mode = None
-        self.flat.finish_capture()
-        if restore is not None:
-            restore()
-            torch.cuda.synchronize()
+        step.graph = torch.cuda.CUDAGraph()
+        with self.flat.capturing(step.role, self.opt.state if in_graph and step.world == 1 else None), \
+                _gc_paused(), torch.cuda.graph(step.graph):
+            step.loss = self._fwd_bwd(step.static, step.geo.static_geo if step.geo is not None else None)
+            if step.role is not None:
+                self._accumulate_scalars()
+            if in_graph:
+                self._captured_update(step.world)
         # A metered step: the loss tensors the meter launch reads live in THIS graph's pool and belong to this
-        # replay closure (StepCache keeps several graphs alive; the trainer's own reference moves on with every
-        # forward).  In the graph, the captured launch holds their addresses; outside, the eager update gets them.
-        metered = self.meter is not None
-        scalars = self._loss_scalars if metered else None
-        one_deep = not switches.env_on("DEMF_GEO_TWO_DEEP")         # A/B: see replay()
-
-        def replay(next_points=None):
-            """``run`` behind the gradient-accumulation checks: the role this step was captured in must be the one
-            ``trainer.micro`` asks for (last <=> micro == W-1) and ``accumulate`` must be what it was at the
-            capture; nothing has been touched when it refuses.  Advances ``micro``."""
-            if self._accumulate != W_c:
-                raise RuntimeError("this step was captured with accumulate = %d and the trainer now has accumulate "
-                                   "= %d: capture again" % (W_c, self._accumulate))
-            if role is None:
-                return run(next_points)
-            if (role == "last") != (self.micro == W_c - 1):
-                raise RuntimeError("this step was captured in the '%s' role and the trainer is at micro = %d of "
-                                   "accumulate = %d, which takes the '%s' role"
-                                   % (role, self.micro, W_c, "last" if self.micro == W_c - 1 else "accumulate"))
-            self._refuse_overlap()
-            out = run(next_points)
-            self.micro = 0 if role == "last" else self.micro + 1
-            return out
-
-        def run(next_points=None):
-            """One training step.  Default (one-deep): ``next_points`` is the cloud of the NEXT batch;
-            its coordinate pre-pass is launched on the side stream in front of the step's graph and
-            runs underneath the forward (with ``DEMF_GEO_AT_BWD=1``: between the forward and the
-            backward graph); the result is moved into the static buffers at the end of the call.
-            ``DEMF_GEO_TWO_DEEP=1``: ``next_points`` is the cloud of the batch AFTER the next one;
-            the pre-pass is launched after the backward and runs underneath the optimizer update and
-            the first layers of the next forward (measured: 7.80 vs 7.67 ms/step - the forward's
-            statically striped pooled GEMMs lose more to the occupied CUs than the backward does;
-            the step alone is 7.03 ms).  Any other usage stays correct: ``load`` checks whether the
-            static / in-flight geometry belongs to the very tensor object it is given (same object,
-            same version) and otherwise recomputes it.  ``next_points=None`` recomputes the
-            pre-pass of the cloud last given (every step still pays for one full pre-pass)."""
-            main = torch.cuda.current_stream()
-            if (self.meter is not None) != metered:
-                raise RuntimeError("this step was captured %s a step meter and the trainer now has %s: capture again"
-                                   % (("with", "none") if metered else ("without", "one")))
-            if update_in_graph:
-                w_now, stub_now, _ = self.allreduce_config()
-                if w_now != world_c or stub_now:
-                    raise RuntimeError("this step was captured with its optimizer update inside the graph "
-                                       "(world %d, no all-reduce stub); capture again with update_in_graph=False"
-                                       % world_c)
-            update = (lambda defer=False: None) if (update_in_graph or role == "accumulate") else \
-                self._update if not metered else (lambda defer=False: self._update(defer, scalars=scalars))
-            if can_prefetch and switches.env_on("DEMF_SKIP_GEO"):     # measurement only: the step alone
-                self.flush()
-                graph.replay()
-                if graph_bwd is not None:
-                    graph_bwd.replay()
-                update()
-                return loss
-            if graph_bwd is not None:
-                self.flush()
-            if graph_bwd is not None and one_deep:
-                graph.replay()
-                geo.launch_prepass(main, next_points)
-                graph_bwd.replay()
-                update()
-                geo.take_fresh(main)
-                return loss
-            if graph_bwd is not None:
-                graph.replay()
-                graph_bwd.replay()
-                if geo.state["fresh"] is not None:
-                    geo.take_fresh(main)              # no stall: that pre-pass had a whole step
-                geo.launch_prepass(main, next_points)
-                update()
-                return loss
-            if can_prefetch:
-                # single-graph step (the default): the pre-pass goes first - enqueueing the
-                # ~900-node step graph takes the host about a millisecond
-                # (the owed update - norm + AdamW behind an overlapped collective - goes in front of the pre-pass
-                # launch: behind it the step measured 0.17 ms slower, profiles/r05_allreduce_overlap_probe.log)
-                self.flush()
-                geo.launch_prepass(main, next_points)
-            self.flush()
-            graph.replay()
-            update(defer=True)
-            if can_prefetch:
-                geo.take_fresh(main)
-            return loss
-
-        def load(new, skip_geo=False):
-            """Copy another batch into the static input buffers of the captured step.  The captured
-            forward reads its FPS / ball-query / 3-NN indices from the static geometry buffers; if
-            they do not hold THIS cloud's geometry, it is fetched from the finished / in-flight
-            pre-pass (waiting for it) or recomputed here, so geometry and targets can never belong
-            to different batches.  ``skip_geo``: the caller has done that already (DoubleBufferedStep:
-            on the main stream, while this call runs on its input stream)."""
-            if can_prefetch and not skip_geo:
-                geo.ensure(torch.cuda.current_stream(), new["points"], static["points"])
-            static["points"].copy_(new["points"])
-            if ("img_features" in new) != (feats is not None):
-                raise ValueError("load(): the captured step %s an image pyramid, the new batch %s"
-                                 % (("has", "has none") if feats is not None else ("has no", "brings one")))
-            nf = new.get("img_features")
-            metas_done = nf is None
-            if nf is None:
-                pass
-            elif tok_static is not None and not isinstance(nf, dict):
-                # the padding mask the conversion zeroes by is the NEW batch's: constants first
-                head.refresh_metas(static["img_metas"], new["img_metas"])
-                metas_done = True
-                if head.pyramid_tokens(nf, static["img_metas"], out=tok_static) is None:
-                    # (non-contiguous / non-fp32 maps or maps that require grad: the conversion did not run and
-                    # the static token buffer would silently keep the previous batch's image features)
-                    raise ValueError("load(): the new pyramid cannot be converted in place (it must be contiguous "
-                                     "fp32 NCHW maps without requires_grad, as the captured batch's)")
-            elif isinstance(nf, dict):
-                if tok_static is not None and not nf.get("padding_zeroed"):
-                    raise ValueError("this step was captured on a pyramid of feature maps: load() takes maps "
-                                     "(or tokens built by DeMFVoteHead.pyramid_tokens)")
-                static["img_features"]["tokens"].copy_(nf["tokens"])
-            else:
-                for d, f in zip(static["img_features"], nf):
-                    d.copy_(f)
-            if G is not None:
-                nb = [b.tensor if hasattr(b, "tensor") else b for b in new["gt_bboxes_3d"]]
-                if len(nb) <= 32 and all(b.is_cuda for b in nb) and all(l.is_cuda for l in new["gt_labels_3d"]):
-                    # device lists: padded straight into the static buffers (one launch, no copies)
-                    if max(int(b.shape[0]) for b in nb) > G:
-                        raise ValueError("a scene has more ground-truth boxes than the captured step's %d slots" % G)
-                    from . import ops
-                    ops.pad_gt_lists(nb, list(new["gt_labels_3d"]), G,
-                                     out=(static["gt_bboxes_3d"], static["gt_labels_3d"]))
-                else:
-                    g2, l2 = self.pad_targets(new["gt_bboxes_3d"], new["gt_labels_3d"], G, dev)
-                    static["gt_bboxes_3d"].copy_(g2)
-                    static["gt_labels_3d"].copy_(l2)
-            else:
-                static["gt_bboxes_3d"].copy_(new["gt_bboxes_3d"])
-                static["gt_labels_3d"].copy_(new["gt_labels_3d"])
-            if not metas_done and head is not None and hasattr(head, "refresh_metas"):
-                head.refresh_metas(static["img_metas"], new["img_metas"])
-
-        replay.load = load
-        replay.role = role
-        replay.accumulate = W_c
-        replay.update_in_graph = update_in_graph
-        replay.metered = metered
-        replay.static = static
-        replay.geo = geo
-        replay.max_gt = G
-        self._graph = graph
-        return replay
+        # step (StepCache keeps several graphs alive; the trainer's own reference moves on with every forward).
+        # In the graph, the captured launch holds their addresses; outside, the eager update gets them.
+        step.scalars = self._loss_scalars if step.metered else None
 
     def capture_double(self, batch_a, batch_b, **kw):
         """Two captured steps over two sets of static input buffers (``DoubleBufferedStep``): the next batch is
@@ -1159,39 +999,196 @@ class _GeoPipe:
         # one launch instead of one copy per index tensor (~30 of them)
         pairs = [(d, s) for d, s in zip(static_flat, fresh) if d.numel()]
         self.refresh = ops.MultiCopy([d for d, _ in pairs], [s for _, s in pairs])
-        # Which cloud the static geometry buffers hold and which cloud's pre-pass sits in `fresh`
-        # (in flight or finished).
-        captured = _Cloud(points)
-        self.state = dict(static=captured, fresh=None, pts=captured)   # static_pts holds the captured cloud
+        # Which cloud the static geometry buffers hold, which cloud's pre-pass sits in `fresh` (in flight or
+        # finished; None: consumed) and which cloud static_pts holds: the captured one, three times.
+        self.in_static = self.in_pts = _Cloud(points)
+        self.in_fresh = None
 
     def take_fresh(self, main):
         """fresh -> static (one launch), after the pre-pass that filled `fresh` has finished."""
         main.wait_stream(self.side)
         self.refresh()
-        self.state["static"], self.state["fresh"] = self.state["fresh"], None
+        self.in_static, self.in_fresh = self.in_fresh, None
 
     def launch_prepass(self, main, next_points):
         if next_points is not None:
             self.static_pts.copy_(next_points)
-            self.state["pts"] = _Cloud(next_points)
+            self.in_pts = _Cloud(next_points)
         self.side.wait_stream(main)                # the cloud is in place, `fresh` has been consumed
         with torch.cuda.stream(self.side):
             self.graph.replay()
-        self.state["fresh"] = self.state["pts"]
+        self.in_fresh = self.in_pts
 
     def ensure(self, main, points, static_points=None):
         """Make the static index buffers describe ``points``: already there, taken from the finished /
         in-flight pre-pass (waiting for it), or recomputed here."""
-        st = self.state
-        if st["static"].holds(points) or (static_points is not None and st["static"].holds(static_points)
-                                          and points is static_points):
+        if self.in_static.holds(points) or (static_points is not None and self.in_static.holds(static_points)
+                                            and points is static_points):
             return
-        if st["fresh"] is not None and st["fresh"].holds(points):
+        if self.in_fresh is not None and self.in_fresh.holds(points):
             self.take_fresh(main)
         else:
             # (an unrelated pre-pass in flight is left to finish; its result is dropped)
             self.launch_prepass(main, points)
             self.take_fresh(main)
+
+
+class CapturedStep:
+    """One captured training step (``Trainer.capture``): the static input buffers its hipGraph reads, ``load`` to
+    fill them with another batch, and the call that runs it.  ``role`` / ``accumulate`` / ``update_in_graph`` /
+    ``metered`` are what it was captured as, ``max_gt`` the ground-truth slots per scene (``None``: the targets
+    came padded), ``geo`` the pre-pass pipeline (``None``: the graph computes its geometry itself), ``graph`` the
+    hipGraph and ``loss`` the tensor every replay writes the step's loss into."""
+
+    def __init__(self, trainer, batch, max_gt, role, update_in_graph, world):
+        """Builds the static inputs out of ``batch``; the trainer warms up on them and sets ``geo``, ``graph``,
+        ``loss`` and ``scalars`` (with a meter: the loss terms in the graph's pool)."""
+        self.trainer, self.world = trainer, world
+        self.role, self.accumulate, self.update_in_graph = role, trainer._accumulate, update_in_graph
+        self.metered = trainer.meter is not None
+        self.geo = self.graph = self.loss = self.scalars = None
+        dev = batch["points"].device
+        if isinstance(batch["gt_bboxes_3d"], (list, tuple)) and dev.type == "cuda":
+            G = max_gt or max(1, max(int((b.tensor if hasattr(b, "tensor") else b).shape[0])
+                                     for b in batch["gt_bboxes_3d"]))
+            gt, lab = trainer.pad_targets(batch["gt_bboxes_3d"], batch["gt_labels_3d"], G, dev)
+        else:
+            G, gt, lab = None, batch["gt_bboxes_3d"], batch["gt_labels_3d"]
+        self.max_gt = G
+        feats = batch.get("img_features")            # None: a points-only batch - every image block is skipped
+        self.has_image = feats is not None
+        self.head = head = getattr(trainer.model, "pts_bbox_head", None) if feats is not None else None
+        # A pyramid handed over as the reference's list of (B,C,H_l,W_l) maps: the captured step reads TOKENS
+        # (channels-last rows, padding zeroed) from a static buffer, and ``load`` converts every new batch
+        # straight out of the caller's maps into that buffer (one tiled-transpose launch) - instead of copying
+        # the 152 MB pyramid into static maps and transposing those inside the graph.
+        self.tok_static = tok = None
+        if (feats is not None and not isinstance(feats, dict) and dev.type == "cuda" and hasattr(head, "pyramid_tokens")
+                and switches.env_int("DEMF_ZERO_COPY_TOKENS")):
+            self.tok_static = tok = head.pyramid_tokens(feats, batch["img_metas"])
+        if feats is None:
+            self.static = dict(points=batch["points"].clone(), gt_bboxes_3d=gt, gt_labels_3d=lab)
+        else:
+            self.static = dict(points=batch["points"].clone(),
+                               img_features=(tok if tok is not None else
+                                             dict(feats, tokens=feats["tokens"].clone())
+                                             if isinstance(feats, dict) else [f.clone() for f in feats]),
+                               img_metas=batch["img_metas"], gt_bboxes_3d=gt, gt_labels_3d=lab)
+        if head is not None and hasattr(head, "pin_metas"):
+            head.pin_metas(self.static["img_metas"])     # the graph holds raw pointers into its cache entry
+
+    def __call__(self, next_points=None):
+        """One training step behind the gradient-accumulation checks: the role this step was captured in must be
+        the one ``trainer.micro`` asks for (last <=> micro == W-1) and ``accumulate`` must be what it was at the
+        capture; nothing has been touched when it refuses.  Advances ``micro``.  ``next_points``: see ``_run``."""
+        tr, W = self.trainer, self.accumulate
+        if tr._accumulate != W:
+            raise RuntimeError("this step was captured with accumulate = %d and the trainer now has accumulate "
+                               "= %d: capture again" % (W, tr._accumulate))
+        if self.role is None:
+            return self._run(next_points)
+        if (self.role == "last") != (tr.micro == W - 1):
+            raise RuntimeError("this step was captured in the '%s' role and the trainer is at micro = %d of "
+                               "accumulate = %d, which takes the '%s' role"
+                               % (self.role, tr.micro, W, "last" if tr.micro == W - 1 else "accumulate"))
+        tr._refuse_overlap()
+        out = self._run(next_points)
+        tr.micro = 0 if self.role == "last" else tr.micro + 1
+        return out
+
+    def _run(self, next_points):
+        """``next_points`` is the cloud of the NEXT batch: its coordinate pre-pass is launched on the side stream
+        in front of the step's graph (enqueueing the ~900-node graph takes the host about a millisecond) and runs
+        underneath the forward; the result is moved into the static buffers at the end of the call.  Any other
+        usage stays correct: ``load`` checks whether the static / in-flight geometry belongs to the very tensor
+        object it is given (same object, same version) and otherwise recomputes it.  ``next_points=None``
+        recomputes the pre-pass of the cloud last given (every step still pays for one full pre-pass)."""
+        tr, geo = self.trainer, self.geo
+        main = torch.cuda.current_stream()
+        if (tr.meter is not None) != self.metered:
+            raise RuntimeError("this step was captured %s a step meter and the trainer now has %s: capture again"
+                               % (("with", "none") if self.metered else ("without", "one")))
+        if self.update_in_graph:
+            w_now, stub_now, _ = tr.allreduce_config()
+            if w_now != self.world or stub_now:
+                raise RuntimeError("this step was captured with its optimizer update inside the graph "
+                                   "(world %d, no all-reduce stub); capture again with update_in_graph=False"
+                                   % self.world)
+        # the owed update - norm + AdamW behind an overlapped collective - goes in front of the pre-pass launch
+        # (behind it the step measured 0.17 ms slower, profiles/r05_allreduce_overlap_probe.log).  This one call
+        # serves the whole step: ``flush`` clears ``_pending_update`` and only ``_update`` below sets it again -
+        # ``launch_prepass`` touches nothing of the trainer - so a second one in front of the graph would do nothing.
+        tr.flush()
+        if geo is not None and switches.env_on("DEMF_SKIP_GEO"):     # measurement only: the step alone
+            self.graph.replay()
+            self._update()
+            return self.loss
+        if geo is not None:
+            geo.launch_prepass(main, next_points)
+        self.graph.replay()
+        self._update(defer=True)
+        if geo is not None:
+            geo.take_fresh(main)
+        return self.loss
+
+    def _update(self, defer=False):
+        """The eager tail of a replay whose graph does not hold the update: collective, norm, meter, AdamW."""
+        if not (self.update_in_graph or self.role == "accumulate"):
+            self.trainer._update(defer, scalars=self.scalars)
+
+    def load(self, new, skip_geo=False):
+        """Copy another batch into the static input buffers of the captured step.  The captured forward reads its
+        FPS / ball-query / 3-NN indices from the static geometry buffers; if they do not hold THIS cloud's
+        geometry, it is fetched from the finished / in-flight pre-pass (waiting for it) or recomputed here, so
+        geometry and targets can never belong to different batches.  ``skip_geo``: the caller has done that
+        already (DoubleBufferedStep: on the main stream, while this call runs on its input stream)."""
+        static, head, tok_static, G = self.static, self.head, self.tok_static, self.max_gt
+        if self.geo is not None and not skip_geo:
+            self.geo.ensure(torch.cuda.current_stream(), new["points"], static["points"])
+        static["points"].copy_(new["points"])
+        if ("img_features" in new) != self.has_image:
+            raise ValueError("load(): the captured step %s an image pyramid, the new batch %s"
+                             % (("has", "has none") if self.has_image else ("has no", "brings one")))
+        nf = new.get("img_features")
+        metas_done = nf is None
+        if nf is None:
+            pass
+        elif tok_static is not None and not isinstance(nf, dict):
+            # the padding mask the conversion zeroes by is the NEW batch's: constants first
+            head.refresh_metas(static["img_metas"], new["img_metas"])
+            metas_done = True
+            if head.pyramid_tokens(nf, static["img_metas"], out=tok_static) is None:
+                # (non-contiguous / non-fp32 maps or maps that require grad: the conversion did not run and
+                # the static token buffer would silently keep the previous batch's image features)
+                raise ValueError("load(): the new pyramid cannot be converted in place (it must be contiguous "
+                                 "fp32 NCHW maps without requires_grad, as the captured batch's)")
+        elif isinstance(nf, dict):
+            if tok_static is not None and not nf.get("padding_zeroed"):
+                raise ValueError("this step was captured on a pyramid of feature maps: load() takes maps "
+                                 "(or tokens built by DeMFVoteHead.pyramid_tokens)")
+            static["img_features"]["tokens"].copy_(nf["tokens"])
+        else:
+            for d, f in zip(static["img_features"], nf):
+                d.copy_(f)
+        if G is not None:
+            nb = [b.tensor if hasattr(b, "tensor") else b for b in new["gt_bboxes_3d"]]
+            if len(nb) <= 32 and all(b.is_cuda for b in nb) and all(l.is_cuda for l in new["gt_labels_3d"]):
+                # device lists: padded straight into the static buffers (one launch, no copies)
+                if max(int(b.shape[0]) for b in nb) > G:
+                    raise ValueError("a scene has more ground-truth boxes than the captured step's %d slots" % G)
+                from . import ops
+                ops.pad_gt_lists(nb, list(new["gt_labels_3d"]), G,
+                                 out=(static["gt_bboxes_3d"], static["gt_labels_3d"]))
+            else:
+                g2, l2 = self.trainer.pad_targets(new["gt_bboxes_3d"], new["gt_labels_3d"], G,
+                                                  static["points"].device)
+                static["gt_bboxes_3d"].copy_(g2)
+                static["gt_labels_3d"].copy_(l2)
+        else:
+            static["gt_bboxes_3d"].copy_(new["gt_bboxes_3d"])
+            static["gt_labels_3d"].copy_(new["gt_labels_3d"])
+        if not metas_done and head is not None and hasattr(head, "refresh_metas"):
+            head.refresh_metas(static["img_metas"], new["img_metas"])
 
 
 class DoubleBufferedStep:

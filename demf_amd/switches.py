@@ -40,8 +40,8 @@ TABLE = {
     "DEMF_ZERO_COPY_TOKENS": (1, "captured step reads the image tokens in place"),
     "DEMF_DIST_BACKEND": (None, "string: torch.distributed backend (default nccl on a GPU, gloo otherwise)"),
     # present means on, whatever the value ("0" included): bench.py reads DEMF_GEO_AT_BWD this way too
-    "DEMF_GEO_AT_BWD": (None, "present = forward and backward as two graphs, pre-pass started in between"),
-    "DEMF_GEO_TWO_DEEP": (None, "present = coordinate pre-pass two steps ahead"),
+    "DEMF_GEO_AT_BWD": (None, "retired: capture() refuses (was: forward and backward as two graphs, pre-pass between)"),
+    "DEMF_GEO_TWO_DEEP": (None, "retired: capture() refuses (was: coordinate pre-pass two steps ahead)"),
     "DEMF_SKIP_GEO": (None, "present = replay without the pre-pass (measurement only)"),
     "DEMF_SHARE_DEVICE": (None, "present = every rank on GPU 0 (test hook, with DEMF_DIST_BACKEND=gloo)"),
 }

@@ -159,8 +159,8 @@ def test_replay_with_changing_batches_matches_eager(ahead):
     """The captured step fed through its static input buffers (load()) with the pipelined
     pre-pass: three different batches (points, image features, metas, GT counts) cycled through
     the graph give the same losses and parameters as eager steps on them - with next_points = the
-    next batch (the default one-deep contract), = the batch after the next (the DEMF_GEO_TWO_DEEP
-    contract; under the default placement load() then recomputes) and with no prefetch at all
+    next batch (the one-deep contract), = the batch after the next (a caller that runs two ahead, as the
+    retired two-deep replay order did; load() then recomputes) and with no prefetch at all
     (load() recomputes the geometry): the tags keep every usage correct, only the overlap differs."""
     batches = [_tiny_batch(11, 4), _tiny_batch(12, 2), _tiny_batch(13, 5)]
     # a small learning rate keeps the two runs from drifting apart through the (legitimately
