@@ -51,6 +51,7 @@ SIGNATURES = {
     "demf_nchw_to_tokens": [_c_int] * 5 + [_ptr] * 4,
     "demf_pyramid_to_tokens": [_c_int] * 4 + [_ptr] * 5,
     "demf_pyramid_to_tokens_bf16": [_c_int] * 4 + [_ptr] * 5,
+    "demf_tokens_assemble": [_c_int] * 4 + [ctypes.c_longlong] * 2 + [_ptr, _c_int] + [_ptr] * 7 + [_c_int, _ptr],
     "demf_vote_targets": [_c_int] * 4 + [_ptr] * 8,
     "demf_box_extent_count": [_c_int] * 4 + [_ptr] * 8,
     "demf_aligned_nms": [_c_int, _c_int, _c_float] + [_ptr] * 6,

@@ -123,6 +123,49 @@ class ChannelMapper(nn.Module):
         return tuple(outs)
 
 
+def _conv_out(n, conv, axis):
+    """Output extent of ``conv`` (an nn.Conv2d) along ``axis`` for an input extent ``n``."""
+    k, s, p, d = conv.kernel_size[axis], conv.stride[axis], conv.padding[axis], conv.dilation[axis]
+    return (n + 2 * p - d * (k - 1) - 1) // s + 1
+
+
+def pyramid_level_shapes(shape, backbone=None, neck=None):
+    """The (h, w) of every level the neck emits for a padded input of ``shape`` = (Hp, Wp), without running anything:
+    the extents are walked through the modules' own convolution parameters (stem, the pooling of ``ResNet50.forward``,
+    every bottleneck's strided 3x3, the neck's 1x1 levels and its extra 3x3 stride-2 levels on top).  Without modules:
+    the reference geometry (``ResNet50()`` + ``ChannelMapper`` as ``ImageStream()`` builds them: strides 8 / 16 / 32
+    and one extra level).  The frozen-feature cache sizes its arena and a batch's canvas from this."""
+    if backbone is None or neck is None:
+        backbone, neck = _reference_geometry()
+    out = []
+    for axis in (0, 1):
+        n = _conv_out(int(shape[axis]), backbone.conv1, axis)
+        n = (n + 2 * 1 - 3) // 2 + 1                   # F.max_pool2d(x, 3, stride=2, padding=1) in ResNet50.forward
+        taps = []
+        for i in range(4):
+            for blk in getattr(backbone, f"layer{i + 1}"):
+                for conv in (blk.conv1, blk.conv2, blk.conv3):
+                    n = _conv_out(n, conv, axis)
+            if i in backbone.out_indices:
+                taps.append(n)
+        levels = [_conv_out(t, c.conv, axis) for t, c in zip(taps, neck.convs)]
+        for j, c in enumerate(neck.extra_convs):
+            levels.append(_conv_out(taps[-1] if j == 0 else levels[-1], c.conv, axis))
+        out.append(levels)
+    return [(int(h), int(w)) for h, w in zip(*out)]
+
+
+_REFERENCE_GEOMETRY = []
+
+
+def _reference_geometry():
+    if not _REFERENCE_GEOMETRY:
+        with torch.device("meta"):                     # shapes only: no weight is allocated
+            bb = ResNet50()
+            _REFERENCE_GEOMETRY.append((bb, ChannelMapper(bb.out_channels)))
+    return _REFERENCE_GEOMETRY[0]
+
+
 def sine_positional_encoding(mask, num_feats, temperature=10000, normalize=True,
                              scale=2 * math.pi, eps=1e-6, offset=0.0):
     """mmdet SinePositionalEncoding.forward(mask (B,H,W) bool) -> (B,H,W,2*num_feats), i.e. the

@@ -2378,6 +2378,56 @@ def pyramid_to_tokens(mlvl_feats, zero_mask=None, bf16=False, out=None):
     return out
 
 
+def assemble_tokens(arena, table, indices, level_shapes, zero_mask=None, bf16=False, out=None, *, table_host=None,
+                    indices_host=None):
+    """A batch's image tokens out of the frozen feature cache (``featcache.FeatureCache``; demf_tokens_assemble).
+
+    ``arena`` (rows, C) fp32 or bf16 on the device; ``table`` (N, 1 + 2L) int64 on the device, one row
+    ``[row0, h_0, w_0, .., h_{L-1}, w_{L-1}]`` per scene (its rows start at ``row0``, level after level, each
+    (h_l, w_l) row-major); ``indices`` (B,) int64 dataset indices on the device (repeats allowed); ``level_shapes`` the
+    batch's [(H_l, W_l)].  -> ``out`` (B, S = sum H_l W_l, C), bf16 with ``bf16`` else fp32: a scene's own level sits
+    in the top-left corner of the batch's, every other row - and every row with a non-zero ``zero_mask`` (B,S) byte -
+    is zero.  fp32 -> bf16 rounds to nearest even, as ``tensor.to(torch.bfloat16)``.
+
+    L <= 8 and C % 4 == 0.  Every scene is checked on the host (index inside the table, own level no larger than the
+    batch's, rows inside the arena) before anything is launched; ``table_host`` / ``indices_host`` are host copies for
+    that check (int64 CPU tensors or sequences) - without them the device tensors are read back, which synchronises."""
+    if not isinstance(arena, torch.Tensor) or not arena.is_cuda:
+        raise RuntimeError("arena must be a GPU (HIP) tensor: demf_amd operators have no CPU path")
+    if arena.dtype not in (torch.float32, torch.bfloat16) or arena.dim() != 2 or not arena.is_contiguous():
+        raise ValueError("assemble_tokens: the arena must be a contiguous (rows, C) fp32 or bf16 tensor")
+    _chk(table, "table", torch.int64)
+    _chk(indices, "indices", torch.int64)
+    shapes = [(int(h), int(w)) for h, w in level_shapes]
+    L, C, B = len(shapes), arena.shape[1], indices.numel()
+    S = sum(h * w for h, w in shapes)
+    if table.dim() != 2 or indices.dim() != 1 or table.shape[1] != 1 + 2 * L:
+        raise ValueError(f"assemble_tokens: table must be (N, {1 + 2 * L}) for {L} levels and indices (B,), got "
+                         f"{tuple(table.shape)} and {tuple(indices.shape)}")
+    odt = torch.bfloat16 if bf16 else torch.float32
+    if out is None:
+        out = torch.empty((B, S, C), dtype=odt, device=arena.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (B, S, C)
+              and out.dtype == odt and out.device == arena.device):
+        raise ValueError(f"assemble_tokens: `out` must be a contiguous {(B, S, C)} {odt} tensor on the arena's device")
+    if table.device != arena.device or indices.device != arena.device:
+        raise ValueError("assemble_tokens: all tensors must be on the same device")
+    m = None
+    if zero_mask is not None:
+        m = (zero_mask if zero_mask.dtype == torch.uint8 else zero_mask.to(torch.uint8)).contiguous()
+        if not m.is_cuda or tuple(m.shape) != (B, S) or m.device != arena.device:
+            raise ValueError(f"assemble_tokens: zero_mask must be {(B, S)} on the arena's device")
+    th = torch.as_tensor(table if table_host is None else table_host, dtype=torch.int64, device="cpu").contiguous()
+    ih = torch.as_tensor(indices if indices_host is None else indices_host, dtype=torch.int64, device="cpu").contiguous()
+    if tuple(th.shape) != tuple(table.shape) or ih.numel() != B:
+        raise ValueError("assemble_tokens: the host copies do not have the device tensors' shapes")
+    hw = (ctypes.c_int * max(2 * L, 1))(*[v for s in shapes for v in s])
+    _ffi.call("demf_tokens_assemble", B, C, S, L, table.shape[0], arena.shape[0], _p(arena),
+              int(arena.dtype == torch.bfloat16), _p(table), th.data_ptr(), _p(indices), ih.data_ptr(),
+              ctypes.addressof(hw), _p(m), _p(out), int(bool(bf16)), _stream())
+    return out
+
+
 def msda_sample_then_project(tokens, keep4, spatial_shapes, level_start_index, sampling_locations,
                              attention_weights, weight, bias):
     """Multi-scale deformable attention with the value projection applied AFTER sampling:

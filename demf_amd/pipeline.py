@@ -107,15 +107,23 @@ class ScenePipeline:
     """Per-scene host work (``load``) and the batched device work (``to_device``) of one pipeline mode."""
 
     def __init__(self, dataset, mode="train", img_scale=(1333, 800), num_points=20000, seed=0,
-                 img_norm=ops.IMG_NORM, pad_divisor=32, with_img=True):
+                 img_norm=ops.IMG_NORM, pad_divisor=32, with_img=True, image_shapes=None):
         """``with_img=False`` (a points-only model): no image file is opened, nothing of it is uploaded and
         ``image_prep`` is not launched; the batch has no ``img`` and its metas carry no image entries.  Points, random
-        draws and ground truth are those of the ``with_img=True`` pipeline for the same seed."""
+        draws and ground truth are those of the ``with_img=True`` pipeline for the same seed.
+
+        ``with_img=False, image_shapes=mapping`` (training from ``featcache.FeatureCache``): dataset index -> the
+        image's (h, w) as stored on disk.  Still no image file is opened and the batch has no ``img``, but every
+        scene's meta is the complete one of the ``with_img=True`` pipeline, built from the stored shape, and
+        ``to_device`` collates the metas (``batch_input_shape`` = the batch maximum)."""
+        if image_shapes is not None and with_img:
+            raise ValueError("image_shapes stands in for the decoded image: it goes with with_img=False")
         if mode not in ("train", "test"):
             raise ValueError(f"mode must be 'train' or 'test', got {mode!r}")
         self.dataset, self.mode, self.with_img = dataset, mode, bool(with_img)
         self.img_scale, self.num_points, self.seed = tuple(img_scale), int(num_points), int(seed)
         self.img_norm, self.pad_divisor = img_norm, pad_divisor
+        self.image_shapes = image_shapes
 
     def scene_rng(self, index, epoch=0):
         key = [self.seed, epoch, int(index)] if self.mode == "train" else [self.seed, int(index)]
@@ -133,10 +141,14 @@ class ScenePipeline:
         rng = self.scene_rng(index, epoch)
         params = draw_aug_params(rng) if self.mode == "train" else identity_aug_params()
         seed = int(rng.integers(0, 2 ** 63 - 1))
-        if img is None:                             # with_img=False
+        if img is not None:
+            hw = img.shape[:2]
+        else:                                       # with_img=False: no image entries, or those of the stored shape
+            hw = None if self.image_shapes is None else self.image_shapes[int(index)]
+        if hw is None:
             meta = dict(sample_idx=info["sample_idx"], **source_meta, flip=False)
         else:
-            h, w = img.shape[:2]
+            h, w = int(hw[0]), int(hw[1])
             meta = dict(sample_idx=info["sample_idx"], **source_meta,
                         img_filename=info["img_filename"], depth2img=info["depth2img"], flip=False,
                         img_norm_cfg=dict(mean=np.asarray(self.img_norm[0], np.float32),
@@ -253,7 +265,10 @@ class ScenePipeline:
             raw_d, poff_d = self.source_records(big_d, sd, None)
             floor = ops.points_floor(raw_d, poff_d)
             points = ops.points_prep(raw_d, poff_d, floor, sd["params"].view(B, 8), sd["seeds"], self.num_points)
-            batch = dict(points=points, img_metas=[dict(s["meta"]) for s in scenes])
+            metas = [dict(s["meta"]) for s in scenes]
+            if self.image_shapes is not None:       # complete image metas: collated as the image batch's are
+                _, metas = collate_metas(metas, self.pad_divisor)
+            batch = dict(points=points, img_metas=metas)
             if all(s["gt_labels_3d"] is not None for s in scenes):
                 batch["gt_bboxes_3d"] = [torch.from_numpy(np.ascontiguousarray(s["gt_bboxes_3d"])).to(device)
                                          for s in scenes]
@@ -343,15 +358,18 @@ class SceneLoader:
     to its mode (``"train"`` otherwise)."""
 
     def __init__(self, dataset, batch_size, mode=None, seed=0, img_scale=(1333, 800), num_points=20000,
-                 workers=8, drop_last=False, device=None, pipeline=None, with_img=None):
+                 workers=8, drop_last=False, device=None, pipeline=None, with_img=None, image_shapes=None):
         if mode is None:
             mode = "train" if pipeline is None else pipeline.mode
         if pipeline is not None and pipeline.mode != mode:
             raise ValueError(f"the given pipeline is in {pipeline.mode!r} mode, the loader in {mode!r}")
         if pipeline is not None and with_img is not None and bool(with_img) != pipeline.with_img:
             raise ValueError(f"the given pipeline was built with_img={pipeline.with_img}, the loader asks for {with_img}")
+        if pipeline is not None and image_shapes is not None:
+            raise ValueError("image_shapes belongs to the pipeline the loader builds; the given pipeline brings its own")
         self.pipeline = ScenePipeline(dataset, mode, img_scale, num_points, seed,
-                                      with_img=True if with_img is None else with_img) if pipeline is None else pipeline
+                                      with_img=True if with_img is None else with_img,
+                                      image_shapes=image_shapes) if pipeline is None else pipeline
         self.dataset, self.batch_size, self.mode, self.seed = dataset, int(batch_size), mode, int(seed)
         self.drop_last = drop_last
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)

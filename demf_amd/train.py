@@ -4,6 +4,7 @@
                            [--val-ann-file sunrgbd_infos_val.pkl] [--load-from C] [--resume-from C] [--no-validate]
                            [--no-graphs] [--batch-size 16] [--epochs 36] [--seed 0] [--workers 4] [--log-interval 50]
                            [--accumulate 1] [--autoscale-lr] [--model {demf,votenet}]
+                           [--feature-cache DIR [--feature-cache-dtype {fp32,bf16}]]
 
 ``fit`` feeds a dataset through ``SceneLoader(mode="train")``, the frozen image stream and ``engine.Trainer`` (one
 captured hipGraph per batch shape, ``StepCache``).  Losses, gradient norm and learning rate are logged through the
@@ -231,7 +232,7 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
         ckpt_interval=DEFAULTS["ckpt_interval"], max_keep_ckpts=DEFAULTS["max_keep_ckpts"],
         eval_interval=DEFAULTS["eval_interval"], seed=DEFAULTS["seed"], workers=DEFAULTS["workers"], graphs=True,
         resume_from=None, load_from=None, num_points=20000, img_scale=(1333, 800), on_step=None, echo=True,
-        val_batch_size=None, accumulate=DEFAULTS["accumulate"]):
+        val_batch_size=None, accumulate=DEFAULTS["accumulate"], feature_cache=None):
     """Train ``model`` (a ``DeMFVoteNet``: frozen image stream + hot path; or a model without ``extract_img_feat``,
     ``modules.VoteNet``: from points alone - the loader then reads, decodes and uploads no image) on ``train_set`` for
     ``max_epochs`` runner epochs of ``repeat`` passes each.  -> dict(trainer, meter, stepper, epoch, iter, val).
@@ -244,7 +245,12 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
     ``iter``, the meter's ``t``, ``log_interval`` and the log lines count optimizer steps, groups run across the
     ``repeat`` passes of a runner epoch, and the fewer than W batches left over at its end are abandoned
     (``accumulation_plan``; the epoch's last log line carries ``discarded``), so that checkpoints, learning-rate
-    changes and validation fall on step boundaries."""
+    changes and validation fall on step boundaries.
+
+    ``feature_cache`` (a ``featcache.FeatureCache`` of ``train_set`` for this model's image branch): the loader opens
+    no image file (``SceneLoader(with_img=False, image_shapes=cache.ori_shapes)``) and every batch's image features
+    are ``feature_cache.assemble(batch.indices, batch["img_metas"])``; ``model.extract_img_feat`` is not called in
+    the training loop.  Validation still computes the stream: a validation scene is seen once per pass."""
     from . import engine, infer
     from .meter import StepMeter
     from .modules import DeMFHotPath
@@ -254,6 +260,14 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
     if isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1:
         raise ValueError("accumulate must be a positive integer, got %r" % (accumulate,))
     with_img = hasattr(model, "extract_img_feat")
+    if feature_cache is not None:
+        if not with_img:
+            raise ValueError("feature_cache: the model has no image branch")
+        if feature_cache.model is not model or len(feature_cache) != len(train_set):
+            raise ValueError("feature_cache was built for another model or for a dataset of another size")
+        if tuple(feature_cache.img_scale) != tuple(img_scale):
+            raise ValueError("feature_cache holds img_scale %s, the run asks for %s"
+                             % (tuple(feature_cache.img_scale), tuple(img_scale)))
     os.makedirs(work_dir, exist_ok=True)
     torch.manual_seed(seed)                       # (the Trainer seeds the dropout counter from it)
     model.cuda().train()
@@ -277,9 +291,12 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
         check_resume_accumulate(ckpt["meta"], accumulate, resume_from)
         meta = restore_checkpoint(ckpt, model, trainer, meter)
         epoch0, it = int(meta["epoch"]), int(meta["iter"])
+    if feature_cache is not None and (load_from is not None or resume_from is not None):
+        feature_cache.verify()                    # (the weights just loaded must be the ones the cache was built from)
     stepper = trainer.bucketed() if graphs else None
     loader = SceneLoader(train_set, batch_size, "train", seed=seed, img_scale=img_scale, num_points=num_points,
-                         workers=workers, with_img=with_img)
+                         workers=workers, with_img=with_img and feature_cache is None,
+                         image_shapes=None if feature_cache is None else feature_cache.ori_shapes)
     ipe, dropped = accumulation_plan(len(loader), repeat, accumulate)      # iterations per runner epoch
     log = _Log(os.path.join(work_dir, "train.log.json"), echo)
     rows, marks = [], []                          # meter rows not logged yet; (last t, epoch, iter, s/iter) per interval
@@ -315,7 +332,10 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
                 for batch, nxt in _lookahead(loader):
                     step_batch = dict(points=batch["points"], gt_bboxes_3d=batch["gt_bboxes_3d"],
                                       gt_labels_3d=batch["gt_labels_3d"])
-                    if with_img:
+                    if feature_cache is not None:
+                        step_batch.update(img_features=feature_cache.assemble(batch.indices, batch["img_metas"]),
+                                          img_metas=batch["img_metas"])
+                    elif with_img:
                         step_batch.update(img_features=model.extract_img_feat(batch["img"], batch["img_metas"]),
                                           img_metas=batch["img_metas"])
                     micro = trainer.micro
@@ -376,7 +396,16 @@ def parse_args(argv=None):
     p.add_argument("--model", choices=("demf", "votenet"), default="demf",
                    help="demf: DeMFVoteNet (configs/demf/demf_votenet.py); votenet: the points-only class-agnostic "
                         "baseline (configs/baseline/votenet.py), trained without reading an image")
+    p.add_argument("--feature-cache", default=None, metavar="DIR",
+                   help="train from cached image tokens: load the frozen image-feature cache in DIR, or build and "
+                        "save it there; the loop then decodes no image and does not run the image stream")
+    p.add_argument("--feature-cache-dtype", choices=("fp32", "bf16"), default=None,
+                   help="storage of a cache that has to be built (default fp32)")
     args = p.parse_args(argv)
+    if args.feature_cache_dtype is not None and args.feature_cache is None:
+        p.error("--feature-cache-dtype needs --feature-cache")
+    if args.feature_cache is not None and args.model != "demf":
+        p.error("--feature-cache needs a model with an image branch (--model demf)")
     if args.batch_size < 1 or args.workers < 1 or args.log_interval < 1 or args.accumulate < 1:
         p.error("--batch-size, --workers, --log-interval and --accumulate must be positive")
     if args.epochs < 0:
@@ -384,6 +413,37 @@ def parse_args(argv=None):
     if args.load_from and args.resume_from:
         p.error("--load-from and --resume-from exclude each other (a resumed run takes its weights from the checkpoint)")
     return args
+
+
+def open_feature_cache(directory, model, train_set, dtype=None, load_from=None, resume_from=None,
+                       img_scale=(1333, 800), echo=True):
+    """The ``--feature-cache DIR`` of the command line: the weights the run starts from go into ``model`` first (the
+    cache is a function of the image branch; ``fit`` loads them again, which changes nothing), then a valid cache in
+    ``directory`` is loaded - one of ``dtype`` if that is given -, otherwise one is built and saved there."""
+    from . import featcache, infer
+    model.cuda()
+    if load_from is not None:
+        model.load_state_dict(infer._model_state(load_checkpoint_file(load_from)), strict=False)
+    elif resume_from is not None:
+        model.load_state_dict(load_checkpoint_file(resume_from)["state_dict"], strict=False)
+    why = "no cache there"
+    if os.path.exists(os.path.join(directory, featcache.INDEX_FILE)):
+        try:
+            cache = featcache.FeatureCache.load(directory, model, train_set)
+            if (dtype is None or cache.dtype == dtype) and tuple(cache.img_scale) == tuple(img_scale):
+                if echo:
+                    print(f"feature cache {directory}: loaded {len(cache)} scenes, {cache.nbytes} bytes, {cache.dtype}",
+                          flush=True)
+                return cache
+            why = f"it holds {cache.dtype} at img_scale {tuple(cache.img_scale)}"
+            del cache
+        except (ValueError, OSError) as e:
+            why = str(e)
+    if echo:
+        print(f"feature cache {directory}: building ({why})", flush=True)
+    cache = featcache.FeatureCache.build(model, train_set, img_scale=img_scale, dtype=dtype or "fp32")
+    cache.save(directory)
+    return cache
 
 
 def main(argv=None, model=None, **fit_kwargs):
@@ -404,6 +464,10 @@ def main(argv=None, model=None, **fit_kwargs):
     if args.autoscale_lr:
         kw["lr"] = autoscale_lr(DEFAULTS["lr"], args.accumulate)
     kw.update(fit_kwargs)
+    if args.feature_cache is not None:
+        kw["feature_cache"] = open_feature_cache(args.feature_cache, model, train_set, args.feature_cache_dtype,
+                                                 load_from=kw.get("load_from"), resume_from=kw.get("resume_from"),
+                                                 img_scale=kw.get("img_scale", (1333, 800)))
     return fit(model, train_set, args.work_dir, **kw)
 
 

@@ -281,6 +281,18 @@ DEMF_INTERNAL int demf_pyramid_to_tokens(int B, int C, int S, int nlev, const fl
  * demf_msda_{fwd,bwd}_bf16 gather from - BASELINE configs[3], half the bytes of the 152 MB token tensor. */
 DEMF_INTERNAL int demf_pyramid_to_tokens_bf16(int B, int C, int S, int nlev, const float* const* srcs, const int* hws,
                                 const unsigned char* mask, uint16_t* dst, demf_stream_t stream);
+/* A batch's tokens out of the frozen image-feature cache (csrc/featcache.hip).  arena (arena_rows, C), fp32 or bf16
+ * words (arena_bf16); table (N, 1 + 2L) int64 rows [row0, h_0, w_0, ..] on the device, table_host the same on the
+ * host; indices (B) int64 dataset indices on the device (repeats allowed), indices_host the same on the host; hw
+ * (HOST, 2L ints) the batch's level shapes (H_l, W_l), S = sum H_l W_l; mask (B,S) bytes or NULL; out (B,S,C) fp32 or
+ * bf16 words (out_bf16).  Every row of out is written:
+ *   out[b, start_l + y W_l + x] = (y < h_bl && x < w_bl && !mask) ? arena[row0_b + ownstart_bl + y w_bl + x] : 0
+ * fp32 -> bf16 rounds to nearest even.  L <= 8, C % 4 == 0; every scene of the batch is checked against the host
+ * table (index in range, own level <= the batch's, rows inside the arena) before anything is launched.           */
+DEMF_INTERNAL int demf_tokens_assemble(int B, int C, int S, int L, long long N, long long arena_rows, const void* arena,
+                         int arena_bf16, const long long* table, const long long* table_host,
+                         const long long* indices, const long long* indices_host, const int* hw,
+                         const unsigned char* mask, void* out, int out_bf16, demf_stream_t stream);
 
 /* out (N) += column sums of x (R,N; row stride ld).  out arrives zeroed.  The bias gradient of the
  * path's linear layers (mmcv FFN / MultiheadAttention / MultiScaleDeformableAttention projections,
