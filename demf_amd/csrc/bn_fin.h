@@ -32,7 +32,7 @@ struct BnVecFin {
 constexpr int ACC_REPL = 8;
 constexpr int ACC_MAX_N = 1024;                          // channels per layer a block of the ring holds (2N doubles per copy)
 constexpr int ACC_SLOT_DOUBLES = ACC_REPL * 2 * ACC_MAX_N;
-double* accum_slot();   // csrc/mlp.hip: the next zeroed block of the ring (left zeroed by its consumer), or null (A/B off)
+double* accum_slot();   // csrc/launch_state.hip: the next zeroed block of the ring (left zeroed by its consumer), or null (A/B off)
 
 // this workgroup's copy: [sum | second sum] of N doubles each
 __device__ __forceinline__ double* repl_copy(double* __restrict__ racc, int N, int lin) {
@@ -110,7 +110,7 @@ __device__ __forceinline__ void bn_vec_finalize(const BnVecFin& f, int N, int c0
   }
 }
 
-int* sched_slot();   // csrc/mlp.hip: the next self-resetting counter set of the ring
+int* sched_slot();   // csrc/launch_state.hip: the next self-resetting counter set of the ring
 
 // Train-mode BatchNorm bookkeeping of a forward launch (demf_bn_finalize's arguments).  With
 // ss != null the LAST workgroup of a STATS launch turns the column sums into scale / shift, saved

@@ -125,9 +125,9 @@ static inline bool reserve_lds(const void* fn, int bytes, unsigned long long* do
   return true;
 }
 
-// compute dtype switch (demf_set_compute_dtype, csrc/mlp.hip): true = bf16 MFMA, fp32 accumulate
+// compute dtype switch (demf_set_compute_dtype, csrc/launch_state.hip): true = bf16 MFMA, fp32 accumulate
 bool compute_bf16();
-int compute_mode();   // 0 fp32 MFMA, 1 bf16 MFMA, 2 fp32 as three bf16 terms (mlp.hip)
+int compute_mode();   // 0 fp32 MFMA, 1 bf16 MFMA, 2 fp32 as three bf16 terms (launch_state.hip)
 
 // ---- fp32 operands as TWO fp16 terms (kernel template mode CM = 3, P = 2 planes) ------------------------------------
 // x = h + l with h = fp16(x), l = fp16(x - h): 22 significant bits when |x| lies in fp16's normal range, an absolute

@@ -12,7 +12,7 @@
 // (ho*s - pad + kh, wo*s - pad + kw) - or zeros outside the image.  Nothing is unfolded in memory.  128-row x
 // (128 | 64)-column tiles, 4 waves as 2 x 2, K steps of 32 through one LDS stage, three workgroups per CU
 // rotating through load / split / MFMA; fp32-grade arithmetic is the three-term split (x = h + m + l in bf16,
-// six products on v_mfma_f32_32x32x16_bf16, fp32 accumulate - csrc/mlp.hip), the frozen weights arrive pre-split
+// six products on v_mfma_f32_32x32x16_bf16, fp32 accumulate - csrc/mfma.h), the frozen weights arrive pre-split
 // as bf16 planes (P, Cout, KH*KW*Cin) with the BatchNorm scale folded in; P = 1 is the bf16 compute mode.
 // Epilogue: folded-BN bias, the bottleneck's residual add, ReLU.
 // The 7x7 stride-2 stem (Cin = 3) reads the image as NHWC4 (a zero fourth channel): one reduction step = one
@@ -21,12 +21,11 @@
 // Also here: the 3x3 stride-2 max-pool, NCHW -> NHWC4 of the input image, and GroupNorm over NHWC rows written
 // straight into the encoder's token buffer (B, S, 256) - the channels-last hand-over needs no transposition.
 #include "common.h"
+#include "mfma.h"
 
 namespace demf {
 
-using f32x16 = float __attribute__((ext_vector_type(16)));
 using f32x2 = float __attribute__((ext_vector_type(2)));
-using bf16x8 = __bf16 __attribute__((ext_vector_type(8)));
 using bf16x2 = __bf16 __attribute__((ext_vector_type(2)));
 using u32x4 = unsigned __attribute__((ext_vector_type(4)));
 

@@ -18,14 +18,11 @@
 #include <initializer_list>
 
 #include "common.h"
+#include "mfma.h"
 #include <type_traits>
 #include "rng.h"
 
 namespace demf {
-
-using f32x16 = float __attribute__((ext_vector_type(16)));
-using bf16x8 = __bf16 __attribute__((ext_vector_type(8)));
-using bf16x4 = __bf16 __attribute__((ext_vector_type(4)));
 
 // flags / descriptor: include/demf_hip.h (demf_gemm_desc)
 enum {

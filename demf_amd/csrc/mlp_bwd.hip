@@ -8,7 +8,7 @@
 // Until round 2 a layer's backward was two launches here - demf_mlp_gemm_bwd_dx_red (dX = dY.W + the
 // sums of layer l-1) and demf_mlp_gemm_bwd_dw (dW = dY^T.act(Y_{l-1})) - each re-reading Y_l (and the
 // upstream gradient) and each re-doing the BN-backward transform dY = gi*dZ + a*y + b, and in the
-// fp32-grade mode (three bf16 terms per operand, csrc/mlp.hip) each splitting its operands per USE.
+// fp32-grade mode (three bf16 terms per operand, csrc/mfma.h) each splitting its operands per USE.
 // Here one workgroup of 4 or 8 waves walks 32-row slabs and
 //   * builds the dY tile ONCE: every wave owns one 32-channel slice of it (32 rows x 32 channels),
 //     loads it as 4-row x 4-channel register patches (full 128-byte lines), applies the BN-backward
@@ -31,13 +31,11 @@
 // Algorithmic HBM bytes per row: 4*(N [Y_l] + N [G, dense only] + K [Y_{l-1}] + K [dX, RED only]).
 #include "common.h"
 #include "bn_fin.h"
+#include "mfma.h"
 #include "wide_map.h"
 
 namespace demf {
 
-using f32x16 = float __attribute__((ext_vector_type(16)));
-using bf16x8 = __bf16 __attribute__((ext_vector_type(8)));
-using bf16x4 = __bf16 __attribute__((ext_vector_type(4)));
 using bf16x2 = __bf16 __attribute__((ext_vector_type(2)));
 
 struct FusedBwdArgs {
@@ -68,7 +66,7 @@ struct FusedBwdArgs {
   int nchunk;
 };
 
-// one fp32 value -> P bf16 planes: P = 1: rounded; P = 3: x = h + m + l exactly (csrc/mlp.hip, mode 2)
+// one fp32 value -> P bf16 planes: P = 1: rounded; P = 3: x = h + m + l exactly (csrc/mfma.h, mode 2)
 template <int P>
 __device__ __forceinline__ void split_planes(float x, __bf16 (&o)[P]) {
   if constexpr (P == 2) {       // two fp16 terms (csrc/common.h): the planes carry fp16 bit patterns
@@ -111,12 +109,7 @@ __device__ __forceinline__ void split_pair(float a, float b, unsigned (&o)[P]) {
 __device__ __forceinline__ unsigned pair_lo(unsigned p0, unsigned p1) { return __builtin_amdgcn_perm(p1, p0, 0x05040100u); }
 __device__ __forceinline__ unsigned pair_hi(unsigned p0, unsigned p1) { return __builtin_amdgcn_perm(p1, p0, 0x07060302u); }
 
-// byte offset of 16-byte chunk `chunk` (0..3) of 64-byte row `row`.  Chunks are XOR-swizzled by bits 2-3
-// of the row: a ds_read_b128 is served in lane groups {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} (+32),
-// and within each group the four rows that share row & 3 (= the same 16-dword bank window) differ in
-// (row >> 2) & 3, so a fragment read (lane = row, same chunk index) touches all 64 banks exactly once.
-// (Measured with the earlier (row >> 1) & 3: SQ_LDS_BANK_CONFLICT = half of all LDS cycles.)
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
+// (LDS chunk swizzle of the 64-byte-row planes: swz, csrc/mfma.h)
 
 template <int P>
 __device__ __forceinline__ void mfma_planes(f32x16& acc, const bf16x8 (&a)[P], const bf16x8 (&b)[P]) {
@@ -725,7 +718,7 @@ constexpr int PB_LDA = PB_K + 4;      // fp32 A copy: row stride (floats)
 constexpr int PB_LDM = PB_K + 4;      // fp32 M in LDS during the prologue
 
 // 128-byte LDS rows (64 bf16): 16-byte chunk c of row r lives at chunk c ^ ((r >> 1) & 7) (as fr_swz<128> in
-// csrc/mlp.hip: a ds_read_b128 lane group then touches every bank once)
+// csrc/mlp_dev.h: a ds_read_b128 lane group then touches every bank once)
 __device__ __forceinline__ int sw128(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
 // One 8-wave workgroup per CU on 64-row slabs (= one group at ns = 64): half the fold rounds per row and twice

@@ -10,7 +10,7 @@
 //
 // Here: one kernel, 128-row x BN-column tiles (BN = 128, or 256 = a whole row when LayerNorm rides in the
 // epilogue), 8 waves as 2 (rows) x 4 (columns), reduction in steps of 32 through a double-buffered LDS tile with
-// ONE barrier per step.  fp32-grade arithmetic is the three-term split of csrc/mlp.hip (x = h + m + l in bf16,
+// ONE barrier per step.  fp32-grade arithmetic is the three-term split of csrc/mfma.h (x = h + m + l in bf16,
 // the six products of weight >= 2^-16 on v_mfma_f32_32x32x16_bf16, fp32 accumulate); the A rows are split once
 // per tile on their way into LDS, the weights - frozen - arrive PRE-split as bf16 planes (P, N, K) and are copied
 // global -> LDS without touching the VALU.  P = 1 is the bf16 compute mode (operands rounded once).
@@ -18,13 +18,12 @@
 // projection: one launch for all three), bias, ReLU, the padding-mask zeroing of value rows, and
 // residual + LayerNorm.  Workgroups are dealt so that all column tiles of a row block run on one XCD.
 #include "common.h"
+#include "mfma.h"
 #include <type_traits>
 
 namespace demf {
 
-using f32x16 = float __attribute__((ext_vector_type(16)));
 using f32x2 = float __attribute__((ext_vector_type(2)));
-using bf16x8 = __bf16 __attribute__((ext_vector_type(8)));
 using bf16x2 = __bf16 __attribute__((ext_vector_type(2)));
 using u32x4 = unsigned __attribute__((ext_vector_type(4)));
 

@@ -1107,7 +1107,7 @@ _POOL_NOY = bool(switches.env_int("DEMF_POOL_NOY"))
 
 # SA1's first layer (4-float rows -> 64 channels) without its (R x 64) output: statistics from the rows'
 # second moments, the consumers rebuild the values they need (csrc/mlp.hip mlp_first_stats_k, ST bit 3 of
-# mlp_fwd_res_kernel; csrc/mlp_bwd.hip ST bit 2).  A/B switch.
+# csrc/mlp_fwd_res.hip mlp_fwd_res_kernel; csrc/mlp_bwd.hip ST bit 2).  A/B switch.
 _SA1_X4 = bool(switches.env_int("DEMF_SA1_X4"))
 
 
@@ -1176,7 +1176,7 @@ def _fwd_plan(R, ld, ns, shapes, training, has_geo, x_requires_grad):
     # bf16 compute mode (BASELINE configs[3]): SA1-shaped stacks (4-float rows -> 64 -> 64 -> 128, the
     # 1 M-row layers that carry most of the step's HBM traffic) keep the raw outputs of layers 1 and 2
     # - and the gradient that flows between their backwards - as bf16 rows; every kernel on that path
-    # is a round-3 kernel that loads / stores them directly (csrc/mlp.hip mlp_fwd_res_kernel,
+    # is a round-3 kernel that loads / stores them directly (csrc/mlp_fwd_res.hip mlp_fwd_res_kernel,
     # csrc/mlp_bwd.hip).  Statistics, pooled extrema, vectors and weight gradients stay fp32.
     store16 = (_COMPUTE_MODE == 1 and not _NO_BF16_STORE and pool and not has_geo and L == 3
                and ld == 4 and not x_requires_grad and R >= 16384 and R % 64 == 0
