@@ -61,6 +61,9 @@ SIGNATURES = {
     "demf_box3d_iou": [_c_int, _c_int] + [_ptr] * 4,
     "demf_eval_match": [_c_int, _c_int, _ptr, _c_int, _c_int] + [_ptr] * 7,
     "demf_eval_ap": [_c_int, _c_int] + [_ptr] * 8,
+    "demf_nms_bev": [_c_int] * 3 + [_c_float, _c_int] + [_ptr] * 7 + [_ptr],
+    "demf_tta_merge": [_c_int] * 4 + [_c_float, _c_int, _c_int] + [_ptr] * 5 + [_c_int] * 3 + [_ptr] * 5 +
+                      [_c_int] * 3 + [_ptr] * 5 + [_ptr],
     "demf_points_floor": [_c_int, _c_int, ctypes.c_longlong] + [_ptr] * 4,
     "demf_points_prep": [_c_int] * 3 + [ctypes.c_longlong] + [_ptr] * 8,
     "demf_image_prep": [_c_int] * 3 + [ctypes.c_longlong] + [_ptr] * 6,

@@ -2,6 +2,7 @@
 
   python -m demf_amd.infer --data-root R --ann-file sunrgbd_infos_val.pkl --checkpoint C
                            [--batch-size 8] [--workers 8] [--out results.pkl] [--no-eval] [--model {demf,votenet}]
+                           [--tta-scales 0.9,1.0,1.1] [--tta-flip] [--tta-mode bev|3d|aligned] [--tta-nms-thr T]
   python -m demf_amd.infer --data-root R --frames manifest.json --checkpoint C --out results.pkl
 
 ``--frames`` runs raw RGB-D frames (``dataset.RGBDFrames``: colour image, 16-bit depth PNG, calibration) through
@@ -10,6 +11,11 @@
 ``run_test`` feeds a dataset through ``SceneLoader(mode="test")`` and ``DeMFVoteNet.predict_into``; the
 detections of every scene stay on the device in one ``DetectionStore`` and nothing in the loop waits for the
 GPU, so the loader's one-batch-ahead overlap holds.  Single process, one GPU.
+
+``--tta-scales`` / ``--tta-flip`` turn on test-time augmentation (tta.py): every scene is prepared in V views (scale-
+major, the unflipped view before the flipped one), the image stream runs once per scene, the head once per view, and
+the views' detections are merged on the device by a per-class rotated NMS.  It works with ``--model votenet`` and with
+``--frames``.  No accuracy figure has been measured with it.
 """
 import argparse
 import json
@@ -23,20 +29,31 @@ from .pipeline import SceneLoader
 
 
 def run_test(model, dataset, batch_size=8, workers=8, num_points=20000, img_scale=(1333, 800), seed=0,
-             store=None, pipeline=None):
+             store=None, pipeline=None, tta=None):
     """Detections of every scene of ``dataset`` in dataset order -> the ``DetectionStore`` holding them (``store``,
     or a new worst-case one).  The last batch may be smaller; there is no host sync inside the loop.  ``pipeline``:
     a test-mode pipeline instance for the loader to use (``FramePipeline`` for raw frames), which then brings its
-    own ``num_points`` / ``img_scale`` / ``seed``."""
+    own ``num_points`` / ``img_scale`` / ``seed`` (and its own ``tta``).  ``tta``: a ``tta.TTACfg``; the loader then
+    prepares every scene's views, one view store of V * batch_size scenes is allocated once and reused, and every
+    batch goes through ``aug_predict_into``."""
     # (a model without an image stream - modules.VoteNet - is fed points alone: no image is read, decoded or uploaded)
     loader = SceneLoader(dataset, batch_size, "test", seed=seed, img_scale=img_scale, num_points=num_points,
                          workers=workers, pipeline=pipeline,
-                         with_img=hasattr(model, "extract_img_feat") if pipeline is None else None)
+                         with_img=hasattr(model, "extract_img_feat") if pipeline is None else None,
+                         tta=tta if pipeline is None else None)
+    if pipeline is not None and tta is not None and pipeline.tta != tta:
+        raise ValueError("the given pipeline was built with another tta than run_test is asked for")
+    tta = loader.pipeline.tta
     model.eval()
     if store is None:
         store = DetectionStore(max(len(dataset), 1), device=loader.device)
+    if tta is None:
+        for batch in loader:
+            model.predict_into(store, **batch)
+        return store
+    view_store = DetectionStore(tta.num_views * int(batch_size), device=loader.device)
     for batch in loader:
-        model.predict_into(store, **batch)
+        model.aug_predict_into(store, **batch, tta=tta, view_store=view_store)
     return store
 
 
@@ -75,9 +92,27 @@ def parse_args(argv=None):
     p.add_argument("--no-eval", action="store_true", help="do not evaluate (then --out is required)")
     p.add_argument("--model", choices=("demf", "votenet"), default="demf",
                    help="demf: DeMFVoteNet; votenet: the points-only class-agnostic baseline (modules.VoteNet)")
+    p.add_argument("--tta-scales", default=None,
+                   help="test-time augmentation: comma-separated point-cloud scale ratios, e.g. 0.9,1.0,1.1")
+    p.add_argument("--tta-flip", action="store_true",
+                   help="test-time augmentation: add the horizontally flipped view of every scale")
+    p.add_argument("--tta-mode", choices=("bev", "3d", "aligned"), default="bev",
+                   help="overlap of the merging NMS: rotated BEV (default), rotated 3-D, axis-aligned BEV")
+    p.add_argument("--tta-nms-thr", type=float, default=None,
+                   help="IoU threshold of the merging NMS (default: the head's test_cfg nms_thr)")
     args = p.parse_args(argv)
     if args.batch_size < 1 or args.workers < 1:
         p.error("--batch-size and --workers must be positive")
+    args.tta = None
+    if args.tta_scales is not None or args.tta_flip:
+        from .tta import TTACfg
+        try:
+            scales = tuple(float(x) for x in (args.tta_scales or "1.0").split(","))
+            args.tta = TTACfg(scales=scales, flip=args.tta_flip, nms_thr=args.tta_nms_thr, mode=args.tta_mode)
+        except ValueError as e:
+            p.error(f"--tta-scales / --tta-flip: {e}")
+    elif args.tta_nms_thr is not None or args.tta_mode != "bev":
+        p.error("--tta-mode and --tta-nms-thr go with --tta-scales / --tta-flip")
     if args.frames:
         args.no_eval = True
         if not args.out:
@@ -96,8 +131,9 @@ def main(argv=None, model=None, **loader_kwargs):
     if args.frames:
         from .pipeline import FramePipeline
         dataset = RGBDFrames(args.data_root, args.frames)
-        loader_kwargs["pipeline"] = FramePipeline(dataset, **{k: loader_kwargs.pop(k) for k in
-                                                             ("num_points", "img_scale", "seed") if k in loader_kwargs})
+        loader_kwargs["pipeline"] = FramePipeline(dataset, tta=args.tta,
+                                                  **{k: loader_kwargs.pop(k) for k in
+                                                     ("num_points", "img_scale", "seed") if k in loader_kwargs})
     else:
         dataset = SUNRGBDDataset(args.data_root, args.ann_file, test_mode=True)
     if model is None:
@@ -105,7 +141,8 @@ def main(argv=None, model=None, **loader_kwargs):
         model = VoteNet() if args.model == "votenet" else DeMFVoteNet()
     load_checkpoint(model, args.checkpoint)
     model.cuda()
-    store = run_test(model, dataset, batch_size=args.batch_size, workers=args.workers, **loader_kwargs)
+    store = run_test(model, dataset, batch_size=args.batch_size, workers=args.workers, tta=args.tta,
+                     **loader_kwargs)
     if args.out:
         with open(args.out, "wb") as f:
             pickle.dump(store.results(), f)

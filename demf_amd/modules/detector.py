@@ -16,6 +16,62 @@ from .head import DeMFVoteHead
 from .pointnet2 import PointNet2SASSG
 
 
+def _view_rows(img_metas, device):
+    """View-major metas (a list over views of per-scene lists) -> the (V * B, 8) fp32 parameter rows of
+    ``ops.tta_merge`` on ``device``, read back from what ``data.augment_3d`` wrote into the metas."""
+    import numpy as np
+    rows = []
+    for metas in img_metas:
+        for m in metas:
+            if m.get("flip", False):
+                raise ValueError("a view's image is flipped (flip=True): the views of a scene share one unflipped "
+                                 "image, only the cloud is augmented")
+            if m.get("pcd_vertical_flip", False):
+                raise ValueError("vertically flipped views are not supported")
+            rot = np.asarray(m.get("pcd_rotation", np.eye(3)), np.float64)          # rotation_z(angle).T
+            t = np.asarray(m.get("pcd_trans", np.zeros(3)), np.float64)
+            rows.append([1.0 if m.get("pcd_horizontal_flip", False) else 0.0, rot[0, 0], rot[0, 1],
+                         float(m.get("pcd_scale_factor", 1.0)), t[0], t[1], t[2], 0.0])
+    return torch.tensor(rows, dtype=torch.float32).to(device, non_blocking=True)
+
+
+def _aug_views(points, img_metas):
+    """Checks of the view lists -> (V, B, points as a list of (B,N,C) tensors)."""
+    for var, name in ((points, "points"), (img_metas, "img_metas")):
+        if not isinstance(var, (list, tuple)):
+            raise TypeError("{} must be a list over views, but got {}".format(name, type(var)))
+    if len(points) != len(img_metas):
+        raise ValueError("num of augmentations ({}) != num of image meta ({})".format(len(points), len(img_metas)))
+    if len(points) < 2:
+        raise ValueError("test-time augmentation takes at least two views")
+    pts = [torch.stack(p) if isinstance(p, (list, tuple)) else p for p in points]
+    B = pts[0].shape[0]
+    if any(p.shape[0] != B for p in pts) or any(len(m) != B for m in img_metas):
+        raise ValueError("every view holds the same scenes: one (B,N,C) tensor and B metas per view")
+    return len(pts), B, pts
+
+
+def _aug_predict_into(head, forward_view, store, points, img_metas, tta, view_store, view_params):
+    """What the two detectors' ``aug_predict_into`` share: every view's detections into ``view_store`` (view-major),
+    then ``tta.merge_views`` into ``store``.  ``forward_view(v, points_v, metas_v)`` -> the head's ``bbox_preds``."""
+    from ..detections import DetectionStore
+    from ..tta import merge_views
+    V, B, pts = _aug_views(points, img_metas)
+    K, C, per_class = head.packed_shape()
+    if tta is not None:
+        tta.check_limits(K, C)
+    if view_store is None:
+        view_store = DetectionStore(V * B, device=pts[0].device)
+    else:
+        view_store.reset()
+    rows = _view_rows(img_metas, "cpu")                                   # (also the metas' checks)
+    rows = view_params if view_params is not None else rows.to(pts[0].device, non_blocking=True)
+    for v in range(V):
+        head.get_bboxes_packed(pts[v], forward_view(v, pts[v], img_metas[v]), img_metas[v], view_store)
+    merge_views(view_store, rows, store, 0, B, head, tta)
+    return view_store
+
+
 class DeMFHotPath(nn.Module):
     def __init__(self, cfg: DeMFCfg = None):
         super().__init__()
@@ -89,7 +145,9 @@ class DeMFVoteNet(DeMFHotPath):
       forward_train(points, img, img_metas, gt_bboxes_3d, gt_labels_3d) -> dict of losses  (:134-170)
       simple_test(points, img_metas, img) -> list of dict(boxes_3d, scores_3d, labels_3d)  (:254-283)
       predict_into(store, points, img_metas, img): the same detections appended to a device-resident store
-      forward_test(points, img_metas, img)  (single-augmentation form of :172-238)
+      forward_test(points, img_metas, img)  (:172-238; lists over augmentations: one -> simple_test, more -> aug_test)
+      aug_test(points, img_metas, img) / aug_predict_into(store, ...): test-time augmentation, which :236-238
+          dispatches to and the reference cannot run - the image stream once, the head per view, merged by tta.py
     """
 
     def __init__(self, cfg: DeMFCfg = None, image_stream=None, **image_stream_kwargs):
@@ -148,17 +206,60 @@ class DeMFVoteNet(DeMFHotPath):
         bbox_preds = self.forward_head(points, img_features, img_metas)
         self.pts_bbox_head.get_bboxes_packed(points, bbox_preds, img_metas, store)
 
+    @torch.no_grad()
+    def aug_predict_into(self, store, points=None, img_metas=None, img=None, tta=None, view_store=None,
+                         view_params=None, **unused):
+        """Test-time augmentation with the detections on the device (tta.py): ``points`` is a list over views of
+        (B,N,C) clouds, ``img_metas`` a list over views of the scenes' metas (``data.augment_3d``'s, which name
+        each view's flip / rotation / scale / translation), ``img`` ONE tensor - or a list whose entries are that
+        tensor: the views share the unaugmented image, so the frozen image stream runs once.  The head runs per
+        view into ``view_store`` (a ``DetectionStore`` of V * B scenes, view-major: made here when not given, else
+        reset; pass one to inspect the views or to reuse its arrays) and ``tta.merge_views`` appends the B merged
+        scenes to ``store``.  ``tta``: a ``tta.TTACfg`` (threshold, mode, ``max_num``; None: the defaults);
+        ``view_params``: the (V * B, 8) device array of parameter rows when the loader made it already.  No host
+        sync (without ``view_params`` one small upload).  -> the view store."""
+        if isinstance(img, (list, tuple)):
+            if not img:
+                raise ValueError("img is an empty list")
+            for other in img[1:]:
+                if other is not img[0] and other.shape != img[0].shape:
+                    raise ValueError("the views of a scene share one image: every entry of img must be the same "
+                                     "tensor (or a copy of it, of the same shape); the first one is used")
+            img = img[0]
+        _aug_views(points, img_metas)
+        _view_rows(img_metas, "cpu")                                        # (a flipped image is refused first)
+        for metas in img_metas:                                             # :180-183
+            for m in metas:
+                m["batch_input_shape"] = tuple(img.shape[-2:])
+        img_features = self.extract_img_feat(img, img_metas[0])
+        return _aug_predict_into(self.pts_bbox_head,
+                                 lambda v, p, metas: self.forward_head(p, img_features, metas),
+                                 store, points, img_metas, tta, view_store, view_params)
+
+    @torch.no_grad()
+    def aug_test(self, points=None, img_metas=None, img=None, tta=None, **unused):
+        """What the reference's ``forward_test`` dispatches ``num_augs > 1`` to (:236-238) and cannot run: the
+        merged detections of the views -> list of dict(boxes_3d, scores_3d, labels_3d), one per scene."""
+        from ..detections import DetectionStore
+        store = DetectionStore(max(len(img_metas[0]), 1) if img_metas else 1, device=self._device())
+        self.aug_predict_into(store, points, img_metas, img, tta=tta)
+        return store.results()
+
+    def _device(self):
+        return next(self.parameters()).device
+
     def forward_test(self, points=None, img_metas=None, img=None, bboxes_2d=None, **kwargs):
-        """:172-238 for one augmentation (the only form the reference implements for points +
-        image): ``points`` / ``img_metas`` / ``img`` are lists over augmentations."""
+        """:172-238: ``points`` / ``img_metas`` / ``img`` are lists over augmentations; one augmentation is
+        ``simple_test``, more go to ``aug_test``."""
         for var, name in ((points, "points"), (img_metas, "img_metas")):
             if not isinstance(var, list):
                 raise TypeError("{} must be a list, but got {}".format(name, type(var)))
         if len(points) != len(img_metas):
             raise ValueError("num of augmentations ({}) != num of image meta ({})".format(
                 len(points), len(img_metas)))
-        if len(points) != 1:
-            raise NotImplementedError("aug_test is not implemented by the reference either (:240-252)")
+        if len(points) != 1:                                                # :236-238
+            kwargs.pop("rescale", None)
+            return self.aug_test(points, img_metas, img, **kwargs)
         for _img, metas in zip(img, img_metas):                             # :180-183
             for m in metas:
                 m["batch_input_shape"] = tuple(_img.shape[-2:])
@@ -175,7 +276,8 @@ class VoteNet(nn.Module):
       forward_train(points, img_metas, gt_bboxes_3d, gt_labels_3d) -> dict of losses
       simple_test(points, img_metas) -> list of dict(boxes_3d, scores_3d, labels_3d)
       predict_into(store, points, img_metas): the same detections appended to a device-resident store
-      forward_test(points, img_metas)  (single-augmentation form)
+      forward_test(points, img_metas)  (lists over augmentations: one -> simple_test, more -> aug_test)
+      aug_test(points, img_metas) / aug_predict_into(store, ...): test-time augmentation (tta.py)
     """
 
     def __init__(self, cfg: VoteNetCfg = None):
@@ -239,6 +341,23 @@ class VoteNet(nn.Module):
         bbox_preds = self.forward_head(points)
         self.bbox_head.get_bboxes_packed(points, bbox_preds, img_metas, store)
 
+    @torch.no_grad()
+    def aug_predict_into(self, store, points=None, img_metas=None, tta=None, view_store=None, view_params=None,
+                         **unused):
+        """``DeMFVoteNet.aug_predict_into`` without the image: lists over views of clouds and metas -> the merged
+        scenes appended to ``store``; no host sync.  -> the view store."""
+        return _aug_predict_into(self.bbox_head, lambda v, p, metas: self.forward_head(p), store, points,
+                                 img_metas, tta, view_store, view_params)
+
+    @torch.no_grad()
+    def aug_test(self, points=None, img_metas=None, tta=None, **unused):
+        """The merged detections of the views -> list of dict(boxes_3d, scores_3d, labels_3d), one per scene."""
+        from ..detections import DetectionStore
+        store = DetectionStore(max(len(img_metas[0]), 1) if img_metas else 1,
+                               device=next(self.parameters()).device)
+        self.aug_predict_into(store, points, img_metas, tta=tta)
+        return store.results()
+
     def forward_test(self, points=None, img_metas=None, **kwargs):
         for var, name in ((points, "points"), (img_metas, "img_metas")):
             if not isinstance(var, list):
@@ -246,9 +365,10 @@ class VoteNet(nn.Module):
         if len(points) != len(img_metas):
             raise ValueError("num of augmentations ({}) != num of image meta ({})".format(
                 len(points), len(img_metas)))
-        if len(points) != 1:
-            raise NotImplementedError("test-time augmentation is not implemented")
         kwargs.pop("img", None)
+        if len(points) != 1:
+            kwargs.pop("rescale", None)
+            return self.aug_test(points, img_metas, **kwargs)
         return self.simple_test(points[0], img_metas[0], **kwargs)
 
 

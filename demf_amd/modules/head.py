@@ -99,6 +99,14 @@ class VoteHeadBase(nn.Module):
                         store.scores, store.labels, store.scene_off, store.state)
         return store
 
+    def packed_shape(self):
+        """-> (K, C, per_class) of ``get_bboxes_packed``: K candidates per scene (``num_proposal`` for every
+        ensemble layer of ``test_cfg``), C classes, and whether a survivor is reported once per class - a scene
+        then holds at most K rows of a class, K * C rows in all (else K rows)."""
+        layers = self.test_cfg.get("ensemble_layers")
+        K = self.num_proposal * (len(layers) if layers is not None else 1)
+        return K, self.num_classes, bool(self.test_cfg["per_class_proposal"])
+
     def _unpack(self, store, input_metas):
         """A batch's store -> the reference's list of (boxes, scores, labels) per scene: one host sync."""
         off, rows = store.host_index()

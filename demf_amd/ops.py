@@ -2131,6 +2131,121 @@ def detect_pack(keep, obj, sem, classes, boxes_bottom, score_thr, per_class, fir
 
 
 # --------------------------------------------------------------------------
+# Test-time augmentation (csrc/tta.hip; tta.merge_views composes these)
+# --------------------------------------------------------------------------
+NMS_MAX_SEGMENT = 1024            # boxes of one NMS segment: V * K of a merge
+TTA_MAX_CANDIDATES = 16384        # V * K * C of a merged scene
+NMS_MODES = {"bev": 0, "aligned": 1, "3d": 2}
+
+
+def _nms_mode(mode):
+    if mode not in NMS_MODES:
+        raise ValueError(f"mode must be one of {sorted(NMS_MODES)}, got {mode!r}")
+    return NMS_MODES[mode]
+
+
+def nms_bev(boxes, scores, seg_start, seg_count, thr, mode="bev", valid=None, n_max=NMS_MAX_SEGMENT, overflow=None):
+    """Segmented greedy NMS (see demf_nms_bev): boxes (R,7) bottom-centre, scores (R,), seg_start / seg_count (S,)
+    int32 on the device; segment s is the rows seg_start[s] .. + seg_count[s].  ``mode``: "bev" rotated footprints
+    (upstream's ``nms_gpu``), "aligned" centre +- (dx, dy) / 2 (``nms_normal_gpu``), "3d" rotated 3-D IoU.  ``valid``
+    (R,) uint8 / bool masks candidates; ``n_max`` is the host's bound on ``seg_count`` (<= 1024).  -> keep (R,) uint8,
+    zero outside the segments.  ``overflow``: a (1,) int32 tensor that receives 1 when a segment holds more than
+    ``n_max`` rows or leaves the arrays (such a segment keeps nothing).  No host sync."""
+    _chk(boxes, "boxes")
+    _chk(scores, "scores")
+    _chk(seg_start, "seg_start", torch.int32)
+    _chk(seg_count, "seg_count", torch.int32)
+    if boxes.dim() != 2 or boxes.shape[1] != 7 or scores.shape != boxes.shape[:1]:
+        raise ValueError(f"nms_bev takes (R,7) boxes and (R,) scores, got {tuple(boxes.shape)} and "
+                         f"{tuple(scores.shape)}")
+    if seg_start.dim() != 1 or seg_start.shape != seg_count.shape:
+        raise ValueError("seg_start and seg_count must be (S,) arrays of one length")
+    R = boxes.shape[0]
+    if valid is not None:
+        valid = valid.contiguous().view(torch.uint8) if valid.dtype == torch.bool else valid
+        _chk(valid, "valid", torch.uint8)
+        if valid.shape != scores.shape:
+            raise ValueError(f"valid must be {tuple(scores.shape)}, got {tuple(valid.shape)}")
+    if overflow is None:
+        overflow = torch.zeros((1,), dtype=torch.int32, device=boxes.device)
+    else:
+        _chk(overflow, "overflow", torch.int32)
+    keep = torch.zeros((R,), dtype=torch.uint8, device=boxes.device)
+    _ffi.call("demf_nms_bev", R, seg_start.numel(), int(n_max), float(thr), _nms_mode(mode), _p(boxes), _p(scores),
+              _p(seg_start), _p(seg_count), _p(valid), _p(keep), _p(overflow), _stream())
+    return keep
+
+
+def tta_merge(view_boxes, view_scores, view_labels, view_scene_off, view_state, params, first_view_scene, B, V, C, K,
+              thr, mode, max_num, first_scene, boxes, scores, labels, scene_off, state):
+    """The merge of a batch's views into the arrays of a ``DetectionStore`` (see demf_tta_merge; the
+    ``DetectionStore``-level caller is ``tta.merge_views``).  view_*: the arrays of the view store, whose scene
+    ``first_view_scene + v * B + b`` is view v of batch scene b; params (V * B, 8) fp32: the rows of
+    ``pipeline.param_row`` in that order.  Nothing is returned and nothing is synchronised; the workspace is sized
+    from the host arguments alone, so the call can be captured."""
+    _chk(view_boxes, "view_boxes")
+    _chk(view_scores, "view_scores")
+    _chk(view_labels, "view_labels", torch.int32)
+    _chk(view_scene_off, "view_scene_off", torch.int32)
+    _chk(view_state, "view_state", torch.int32)
+    _chk(params, "params")
+    _chk(boxes, "boxes")
+    _chk(scores, "scores")
+    _chk(labels, "labels", torch.int32)
+    _chk(scene_off, "scene_off", torch.int32)
+    _chk(state, "state", torch.int32)
+    B, V, C, K = int(B), int(V), int(C), int(K)
+    if params.numel() != V * B * 8:
+        raise ValueError(f"params must be ({V * B}, 8): one row per view scene, got {tuple(params.shape)}")
+    dev = boxes.device
+    rows = B * C * V * K if V * K <= NMS_MAX_SEGMENT and V * K * C <= TTA_MAX_CANDIDATES else 0   # (refused below)
+    ws_boxes = torch.empty((rows, 7), dtype=torch.float32, device=dev)
+    ws_scores = torch.empty((rows,), dtype=torch.float32, device=dev)
+    ws_seg = torch.empty((2 * B * C + 1,), dtype=torch.int32, device=dev)
+    ws_keep = torch.empty((rows,), dtype=torch.uint8, device=dev)
+    _ffi.call("demf_tta_merge", B, V, C, K, float(thr), _nms_mode(mode), int(max_num), _p(view_boxes),
+              _p(view_scores), _p(view_labels), _p(view_scene_off), _p(view_state), int(first_view_scene),
+              view_scene_off.numel() - 1, view_scores.numel(), _p(params), _p(ws_boxes), _p(ws_scores), _p(ws_seg),
+              _p(ws_keep), int(first_scene), scene_off.numel() - 1, scores.numel(), _p(boxes), _p(scores), _p(labels),
+              _p(scene_off), _p(state), _stream())
+
+
+def _nms_single(boxes_xyxyr, scores, thresh, mode, pre_maxsize=None, post_max_size=None):
+    _chk(boxes_xyxyr, "boxes")
+    _chk(scores, "scores")
+    if boxes_xyxyr.dim() != 2 or boxes_xyxyr.shape[1] != 5 or scores.shape != boxes_xyxyr.shape[:1]:
+        raise ValueError(f"boxes must be (n,5) (x1, y1, x2, y2, ry) and scores (n,), got {tuple(boxes_xyxyr.shape)} "
+                         f"and {tuple(scores.shape)}")
+    order = torch.sort(scores, descending=True, stable=True)[1]           # ties: the lower index first
+    if pre_maxsize is not None:
+        order = order[:int(pre_maxsize)]
+    n = order.numel()
+    if n > NMS_MAX_SEGMENT:
+        raise RuntimeError(f"nms of {n} boxes: one segment holds at most {NMS_MAX_SEGMENT} (pass pre_maxsize)")
+    b = boxes_xyxyr[order]
+    b7 = torch.zeros((n, 7), dtype=torch.float32, device=b.device)
+    b7[:, 0], b7[:, 1] = (b[:, 0] + b[:, 2]) / 2, (b[:, 1] + b[:, 3]) / 2
+    b7[:, 3], b7[:, 4], b7[:, 5], b7[:, 6] = b[:, 2] - b[:, 0], b[:, 3] - b[:, 1], 1.0, b[:, 4]
+    seg = torch.tensor([0, n], dtype=torch.int32, device=b.device)
+    keep = nms_bev(b7, scores[order].contiguous(), seg[:1], seg[1:], thresh, mode, n_max=n)
+    kept = order[keep.bool()]                                             # the one sync: sizes the result
+    return kept if post_max_size is None else kept[:int(post_max_size)]
+
+
+def nms_gpu(boxes, scores, thresh, pre_maxsize=None, post_max_size=None):
+    """mmdet3d.ops.iou3d.nms_gpu: rotated BEV NMS of boxes (n,5) = (x1, y1, x2, y2, ry) -> int64 indices of the kept
+    boxes in score order (ties: the lower index first).  One segment of ``nms_bev``, so n (after ``pre_maxsize``) is
+    at most 1024.  Synchronises once, to size its result.  The footprint is the package's own (``box3d_overlaps``):
+    centre ((x1+x2)/2, (y1+y2)/2), size (x2-x1, y2-y1), yaw ry."""
+    return _nms_single(boxes, scores, thresh, "bev", pre_maxsize, post_max_size)
+
+
+def nms_normal_gpu(boxes, scores, thresh):
+    """mmdet3d.ops.iou3d.nms_normal_gpu: ``nms_gpu`` on the axis-aligned rectangles (ry ignored)."""
+    return _nms_single(boxes, scores, thresh, "aligned")
+
+
+# --------------------------------------------------------------------------
 # Indoor detection evaluation (csrc/eval3d.hip; evaluation.indoor_eval composes these)
 # --------------------------------------------------------------------------
 EVAL_MAX_PRED_PER_SEGMENT = 4096

@@ -107,7 +107,7 @@ class ScenePipeline:
     """Per-scene host work (``load``) and the batched device work (``to_device``) of one pipeline mode."""
 
     def __init__(self, dataset, mode="train", img_scale=(1333, 800), num_points=20000, seed=0,
-                 img_norm=ops.IMG_NORM, pad_divisor=32, with_img=True, image_shapes=None):
+                 img_norm=ops.IMG_NORM, pad_divisor=32, with_img=True, image_shapes=None, tta=None):
         """``with_img=False`` (a points-only model): no image file is opened, nothing of it is uploaded and
         ``image_prep`` is not launched; the batch has no ``img`` and its metas carry no image entries.  Points, random
         draws and ground truth are those of the ``with_img=True`` pipeline for the same seed.
@@ -115,7 +115,18 @@ class ScenePipeline:
         ``with_img=False, image_shapes=mapping`` (training from ``featcache.FeatureCache``): dataset index -> the
         image's (h, w) as stored on disk.  Still no image file is opened and the batch has no ``img``, but every
         scene's meta is the complete one of the ``with_img=True`` pipeline, built from the stored shape, and
-        ``to_device`` collates the metas (``batch_input_shape`` = the batch maximum)."""
+        ``to_device`` collates the metas (``batch_input_shape`` = the batch maximum).
+
+        ``tta`` (a ``tta.TTACfg``, test mode only): every scene is prepared in V views.  Records and image bytes are
+        uploaded once and ``points_floor`` runs once; ``points_prep`` runs once per view with that view's parameter
+        rows and sample keys.  The batch then carries ``points`` as a list of V tensors, ``img_metas`` as a list of V
+        lists (each made by ``apply_aug_params`` from the view's parameters), ONE ``img``, and ``view_params``: the
+        (V * B, 8) device array of parameter rows, view-major.  View 0 has the sample key of the single-view batch
+        (and, with a first scale of 1.0, its parameters); view v > 0 draws its key from the scene's generator after
+        that draw, in view order."""
+        if tta is not None and mode != "test":
+            raise ValueError("tta is test-time augmentation: it goes with mode='test'")
+        self.tta = tta
         if image_shapes is not None and with_img:
             raise ValueError("image_shapes stands in for the decoded image: it goes with with_img=False")
         if mode not in ("train", "test"):
@@ -157,9 +168,42 @@ class ScenePipeline:
             meta["pad_shape"] = tuple(meta["batch_input_shape"]) + (3,)
         ann = info.get("ann_info")
         boxes = ann["gt_bboxes_3d"] if ann is not None else np.zeros((0, 7), np.float32)
+        views = None
+        if self.tta is not None:                    # view 0: the draw above; the others draw their keys after it
+            from .tta import view_params
+            views = []
+            for v, p in enumerate(view_params(self.tta)):
+                key = seed if v == 0 else int(rng.integers(0, 2 ** 63 - 1))
+                views.append(dict(params=p, seed=key, meta=apply_aug_params(boxes, meta, p)[1]))
+            params = views[0]["params"]
         boxes, meta = apply_aug_params(boxes, meta, params)
         return dict(index=int(index), img=img, params=params, seed=seed, meta=meta, gt_bboxes_3d=boxes,
-                    gt_labels_3d=None if ann is None else ann["gt_labels_3d"], **source)
+                    gt_labels_3d=None if ann is None else ann["gt_labels_3d"], views=views, **source)
+
+    def _view_words(self, scenes):
+        """-> (parameter rows (V * B, 8) fp32, sample keys (V * B,) int64), view-major; one view without ``tta``."""
+        if self.tta is None:
+            return (np.stack([param_row(s["params"]) for s in scenes]),
+                    np.array([s["seed"] for s in scenes], np.int64))
+        V = self.tta.num_views
+        return (np.stack([param_row(s["views"][v]["params"]) for v in range(V) for s in scenes]),
+                np.array([s["views"][v]["seed"] for v in range(V) for s in scenes], np.int64))
+
+    def _view_points(self, raw_d, poff_d, floor, params, seeds, B):
+        """``points_prep`` once per view: -> the (B, num_points, 4) tensor, or the list of V of them with ``tta``."""
+        params = params.view(-1, 8)
+        if self.tta is None:
+            return ops.points_prep(raw_d, poff_d, floor, params, seeds, self.num_points)
+        return [ops.points_prep(raw_d, poff_d, floor, params[v * B:(v + 1) * B], seeds[v * B:(v + 1) * B],
+                                self.num_points) for v in range(self.tta.num_views)]
+
+    def _view_metas(self, scenes, collate):
+        """The batch's metas (``collate``: through ``collate_metas``): a list per scene, or V of them with ``tta``."""
+        def one(metas):
+            return collate_metas(metas, self.pad_divisor)[1] if collate else [dict(m) for m in metas]
+        if self.tta is None:
+            return one([s["meta"] for s in scenes])
+        return [one([s["views"][v]["meta"] for s in scenes]) for v in range(self.tta.num_views)]
 
     def load(self, index, epoch=0):
         """Host part of one scene: file reads, JPEG decode, random draws, boxes and metadata."""
@@ -205,8 +249,8 @@ class ScenePipeline:
             shp += [h, w, nh, nw]
         big, words = self.pack_source(scenes)
         # every small array as whole 8-byte words of one upload: params (B,8) fp32, the source's, offsets, seeds, shapes
-        words = dict(params=np.stack([param_row(s["params"]) for s in scenes]).reshape(-1), **words, ioff=ioff,
-                     seeds=np.array([s["seed"] for s in scenes], np.int64), shapes=np.array(shp, np.int32))
+        rows, keys = self._view_words(scenes)
+        words = dict(params=rows.reshape(-1), **words, ioff=ioff, seeds=keys, shapes=np.array(shp, np.int32))
         words = {k: np.ascontiguousarray(v).reshape(-1) for k, v in words.items()}
         at, n = {}, 0
         for k, v in words.items():
@@ -218,7 +262,8 @@ class ScenePipeline:
         sm = small.numpy()
         for k, v in words.items():
             sm[at[k][0]:at[k][1]].view(v.dtype)[:] = v
-        (Hp, Wp), metas = collate_metas([s["meta"] for s in scenes], self.pad_divisor)
+        (Hp, Wp), _ = collate_metas([s["meta"] for s in scenes], self.pad_divisor)
+        metas = self._view_metas(scenes, True)
         stream = torch.cuda.current_stream(device) if stream is None else stream
         with torch.cuda.stream(stream):
             big_d = {k: t.to(device, non_blocking=True) for k, t in big.items()}
@@ -228,9 +273,11 @@ class ScenePipeline:
             sd["shapes"] = sd["shapes"].view(B, 4)
             raw_d, poff_d = self.source_records(big_d, sd, img_d)
             floor = ops.points_floor(raw_d, poff_d)
-            points = ops.points_prep(raw_d, poff_d, floor, sd["params"].view(B, 8), sd["seeds"], self.num_points)
+            points = self._view_points(raw_d, poff_d, floor, sd["params"], sd["seeds"], B)
             img = ops.image_prep(img_d, sd["ioff"], sd["shapes"], (Hp, Wp), *self.img_norm)
             batch = dict(points=points, img=img, img_metas=metas)
+            if self.tta is not None:
+                batch["view_params"] = sd["params"].view(-1, 8)
             if all(s["gt_labels_3d"] is not None for s in scenes):
                 batch["gt_bboxes_3d"] = [torch.from_numpy(np.ascontiguousarray(s["gt_bboxes_3d"])).to(device)
                                          for s in scenes]
@@ -244,8 +291,8 @@ class ScenePipeline:
         ``points_prep``) in the same order; no image bytes, offsets or shapes travel and ``image_prep`` is not launched."""
         B = len(scenes)
         big, words = self.pack_source(scenes)
-        words = dict(params=np.stack([param_row(s["params"]) for s in scenes]).reshape(-1), **words,
-                     seeds=np.array([s["seed"] for s in scenes], np.int64))
+        rows, keys = self._view_words(scenes)
+        words = dict(params=rows.reshape(-1), **words, seeds=keys)
         words = {k: np.ascontiguousarray(v).reshape(-1) for k, v in words.items()}
         at, n = {}, 0
         for k, v in words.items():
@@ -264,11 +311,12 @@ class ScenePipeline:
             sd = {k: small_d[a:b].view(getattr(torch, str(words[k].dtype))) for k, (a, b) in at.items()}
             raw_d, poff_d = self.source_records(big_d, sd, None)
             floor = ops.points_floor(raw_d, poff_d)
-            points = ops.points_prep(raw_d, poff_d, floor, sd["params"].view(B, 8), sd["seeds"], self.num_points)
-            metas = [dict(s["meta"]) for s in scenes]
-            if self.image_shapes is not None:       # complete image metas: collated as the image batch's are
-                _, metas = collate_metas(metas, self.pad_divisor)
+            points = self._view_points(raw_d, poff_d, floor, sd["params"], sd["seeds"], B)
+            # (with image_shapes the image metas are complete: collated as the image batch's are)
+            metas = self._view_metas(scenes, self.image_shapes is not None)
             batch = dict(points=points, img_metas=metas)
+            if self.tta is not None:
+                batch["view_params"] = sd["params"].view(-1, 8)
             if all(s["gt_labels_3d"] is not None for s in scenes):
                 batch["gt_bboxes_3d"] = [torch.from_numpy(np.ascontiguousarray(s["gt_bboxes_3d"])).to(device)
                                          for s in scenes]
@@ -284,8 +332,8 @@ class FramePipeline(ScenePipeline):
     counts stay on the device.  Everything else - metadata, point sample, image - is ``ScenePipeline``'s."""
 
     def __init__(self, dataset, img_scale=(1333, 800), num_points=20000, seed=0, img_norm=ops.IMG_NORM,
-                 pad_divisor=32):
-        super().__init__(dataset, "test", img_scale, num_points, seed, img_norm, pad_divisor)
+                 pad_divisor=32, tta=None):
+        super().__init__(dataset, "test", img_scale, num_points, seed, img_norm, pad_divisor, tta=tta)
 
     @staticmethod
     def read_depth(path):
@@ -336,10 +384,14 @@ class SceneBatch(dict):
         """Make ``stream`` (default: the current one) wait for the batch and keep its memory alive there."""
         stream = torch.cuda.current_stream() if stream is None else stream
         stream.wait_event(self.event)
+        def walk(v):
+            if isinstance(v, (list, tuple)):        # (with tta: ``points`` is a list over views)
+                for t in v:
+                    walk(t)
+            elif isinstance(v, torch.Tensor) and v.is_cuda:
+                v.record_stream(stream)
         for v in self.values():
-            for t in (v if isinstance(v, list) else [v]):
-                if isinstance(t, torch.Tensor) and t.is_cuda:
-                    t.record_stream(stream)
+            walk(v)
         return self
 
 
@@ -358,7 +410,9 @@ class SceneLoader:
     to its mode (``"train"`` otherwise)."""
 
     def __init__(self, dataset, batch_size, mode=None, seed=0, img_scale=(1333, 800), num_points=20000,
-                 workers=8, drop_last=False, device=None, pipeline=None, with_img=None, image_shapes=None):
+                 workers=8, drop_last=False, device=None, pipeline=None, with_img=None, image_shapes=None, tta=None):
+        if tta is not None and pipeline is not None:
+            raise ValueError("tta belongs to the pipeline the loader builds; the given pipeline brings its own")
         if mode is None:
             mode = "train" if pipeline is None else pipeline.mode
         if pipeline is not None and pipeline.mode != mode:
@@ -369,7 +423,7 @@ class SceneLoader:
             raise ValueError("image_shapes belongs to the pipeline the loader builds; the given pipeline brings its own")
         self.pipeline = ScenePipeline(dataset, mode, img_scale, num_points, seed,
                                       with_img=True if with_img is None else with_img,
-                                      image_shapes=image_shapes) if pipeline is None else pipeline
+                                      image_shapes=image_shapes, tta=tta) if pipeline is None else pipeline
         self.dataset, self.batch_size, self.mode, self.seed = dataset, int(batch_size), mode, int(seed)
         self.drop_last = drop_last
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)

@@ -916,6 +916,46 @@ DEMF_INTERNAL int demf_eval_ap(int C, int T, const int* cls_off, const int* npos
                  const unsigned char* tp_sorted, int* workspace, double* ap, double* rec, demf_stream_t stream);
 
 /* ------------------------------------------------------------------ *
+ * Test-time augmentation (csrc/tta.hip).  The reference's forward_test hands num_augs > 1 to self.aug_test
+ * (demf/modeling/detectors/demfnet.py:236-238), which it inherits from a class whose members it lacks; mmdet3d
+ * 0.18.1 builds that method from merge_aug_bboxes_3d: bbox3d_mapping_back per view, concatenation, a per-class
+ * iou3d.nms_gpu (rotated BEV) or nms_normal_gpu (axis-aligned BEV), and a score-ordered cut [dep-recall].
+ * Boxes are the bottom-centre form; arithmetic fp32; footprints are those of demf_box3d_iou.
+ * mode: 0 rotated BEV IoU, 1 axis-aligned BEV IoU of centre +- (dx, dy) / 2 (yaw ignored), 2 rotated 3-D IoU;
+ * iou = overlap / max(a + b - overlap, 1e-8); a footprint with dx * dy == 0 overlaps nothing (rotated modes).
+ * ------------------------------------------------------------------ */
+
+/* Segmented greedy NMS.  Segment s = rows seg_start[s] .. seg_start[s] + seg_count[s] of boxes (R,7) / scores (R)
+ * (seg_start, seg_count: S ints on the DEVICE).  Candidates are the rows with valid != 0 (valid may be NULL: all)
+ * whose score is neither NaN nor -inf, visited in score order (descending; ties: the lower row first); a visited
+ * candidate that is still alive is kept and removes every alive candidate with !(iou <= thr), so NaN removes.
+ * keep (R) bytes: 0 / 1 for the rows of every segment; rows outside every segment are not written.  n_max: the host's
+ * bound on seg_count, at most 1024 (beyond: DEMF_EUNSUPPORTED, nothing launched).  A segment whose count exceeds
+ * n_max on the device, or whose rows leave [0, R), sets *overflow = 1 and none of its keep bytes is written.      */
+DEMF_INTERNAL int demf_nms_bev(int R, int S, int n_max, float thr, int mode, const float* boxes, const float* scores,
+                 const int* seg_start, const int* seg_count, const unsigned char* valid, unsigned char* keep,
+                 int* overflow, demf_stream_t stream);
+
+/* The merge of a batch's views (merge_aug_bboxes_3d).  View store = the arrays of a DetectionStore whose scene
+ * first_view_scene + v * B + b is view v of batch scene b (view-major), written by demf_detect_pack with at most
+ * K rows per class and scene; params (V * B, 8) = the rows of demf_points_prep in the same order.  Per (scene, class):
+ * the rows of that label are gathered over the views in (view, row) order and mapped back by the inverse of their
+ * parameter row (centre -= t; [:6] /= scale; centre turned by -angle, yaw += angle; then, if flipped, x -> -x and
+ * yaw -> pi - yaw); demf_nms_bev over the B * C segments; per scene the kept rows ordered by (score descending,
+ * class, view, row ascending), cut at max_num and appended to the destination arrays with demf_detect_pack's
+ * protocol (cursor read at scene_off[first_scene]; scene_off[first_scene + b + 1] and state[0] written; state[1] = 1
+ * when rows do not fit, when a segment holds more than V * K rows, or when view_state[1] (may be NULL) is set; rows at
+ * or beyond max_rows are not written).  Workspace: ws_boxes (B*C*V*K, 7), ws_scores (B*C*V*K), ws_seg (2*B*C + 1)
+ * ints, ws_keep (B*C*V*K) bytes.  Three launches whatever the sizes, no host sync.  V * K > 1024 or
+ * V * K * C > 16384 returns DEMF_EUNSUPPORTED with nothing launched.                                              */
+DEMF_INTERNAL int demf_tta_merge(int B, int V, int C, int K, float thr, int mode, int max_num, const float* view_boxes,
+                   const float* view_scores, const int* view_labels, const int* view_scene_off,
+                   const int* view_state, int first_view_scene, int view_max_scenes, int view_max_rows,
+                   const float* params, float* ws_boxes, float* ws_scores, int* ws_seg, unsigned char* ws_keep,
+                   int first_scene, int max_scenes, int max_rows, float* boxes, float* scores, int* labels,
+                   int* scene_off, int* state, demf_stream_t stream);
+
+/* ------------------------------------------------------------------ *
  * Input pipeline of SUN RGB-D scenes (csrc/pipeline.hip): the per-point and per-pixel steps of the training /
  * test pipelines of configs/demf/demf_votenet.py:184-216 (mmdet3d 0.18.1 / mmcv transforms).  Scenes are
  * ragged: `offsets` (B+1) int64 DEVICE arrays into the concatenated raw buffers; `total` / `src_bytes` is the
