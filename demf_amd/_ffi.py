@@ -98,6 +98,8 @@ SIGNATURES = {
     "demf_multi_add": [_c_int, _ptr, _c_int, _ptr],
     "demf_multi_add_sumsq": [_c_int, _ptr, _c_int, _ptr, _ptr],
     "demf_scalars_accum": [_c_int, _ptr, _ptr, _c_float, _ptr],
+    "demf_store_concat": [_c_int, _ptr, _c_int, _c_int] + [_ptr] * 5 + [_c_int] * 2 + [_ptr] * 5 + [_ptr],
+    "demf_meter_merge": [_c_int, _c_int, _ptr, _ptr, _ptr],
     "demf_mlp_gemm_fwd": [_c_int] * 4 + [_ptr] * 6,
     "demf_mlp_gemm_fwd_pool": [_c_int] * 4 + [_ptr] * 5 + [_c_int] + [_ptr] * 5,
     "demf_mlp_gemm_fwd_bn": [_c_int] * 4 + [_ptr] * 7 + [_c_float, _c_float] + [_ptr] * 7,

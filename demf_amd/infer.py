@@ -3,6 +3,7 @@
   python -m demf_amd.infer --data-root R --ann-file sunrgbd_infos_val.pkl --checkpoint C
                            [--batch-size 8] [--workers 8] [--out results.pkl] [--no-eval] [--model {demf,votenet}]
                            [--tta-scales 0.9,1.0,1.1] [--tta-flip] [--tta-mode bev|3d|aligned] [--tta-nms-thr T]
+                           [--gpus N]
   python -m demf_amd.infer --data-root R --frames manifest.json --checkpoint C --out results.pkl
 
 ``--frames`` runs raw RGB-D frames (``dataset.RGBDFrames``: colour image, 16-bit depth PNG, calibration) through
@@ -10,7 +11,12 @@
 
 ``run_test`` feeds a dataset through ``SceneLoader(mode="test")`` and ``DeMFVoteNet.predict_into``; the
 detections of every scene stay on the device in one ``DetectionStore`` and nothing in the loop waits for the
-GPU, so the loader's one-batch-ahead overlap holds.  Single process, one GPU.
+GPU, so the loader's one-batch-ahead overlap holds.
+
+``--gpus N`` starts N ranks of this module (``ranks.launch``; the reference's ``multi_gpu_test``); under a launcher
+(``RANK`` in the environment) ``main`` joins the process group instead.  Every rank then runs a contiguous shard of
+the dataset into a store of its own, ``ranks.merge_stores`` leaves all detections in dataset order in one store on
+every rank, and rank 0 alone evaluates, prints and writes ``--out``.  Without either: single process, one GPU.
 
 ``--tta-scales`` / ``--tta-flip`` turn on test-time augmentation (tta.py): every scene is prepared in V views (scale-
 major, the unflipped view before the flipped one), the image stream runs once per scene, the head once per view, and
@@ -19,11 +25,13 @@ the views' detections are merged on the device by a per-class rotated NMS.  It w
 """
 import argparse
 import json
+import os
 import pickle
 import sys
 
 import torch
 
+from . import ranks
 from .detections import DetectionStore
 from .pipeline import SceneLoader
 
@@ -35,26 +43,42 @@ def run_test(model, dataset, batch_size=8, workers=8, num_points=20000, img_scal
     a test-mode pipeline instance for the loader to use (``FramePipeline`` for raw frames), which then brings its
     own ``num_points`` / ``img_scale`` / ``seed`` (and its own ``tta``).  ``tta``: a ``tta.TTACfg``; the loader then
     prepares every scene's views, one view store of V * batch_size scenes is allocated once and reused, and every
-    batch goes through ``aug_predict_into``."""
+    batch goes through ``aug_predict_into``.
+
+    In a process group of W > 1 ranks every rank runs its test shard (``pipeline.shard_chunks``) and gets the MERGED
+    store back, all scenes in dataset order (``store`` must then be None); ``tta`` and ``pipeline`` shard the same
+    scene list."""
     # (a model without an image stream - modules.VoteNet - is fed points alone: no image is read, decoded or uploaded)
+    world, rank = ranks.world(), ranks.rank()
     loader = SceneLoader(dataset, batch_size, "test", seed=seed, img_scale=img_scale, num_points=num_points,
                          workers=workers, pipeline=pipeline,
                          with_img=hasattr(model, "extract_img_feat") if pipeline is None else None,
-                         tta=tta if pipeline is None else None)
+                         tta=tta if pipeline is None else None, rank=rank, world=world)
     if pipeline is not None and tta is not None and pipeline.tta != tta:
         raise ValueError("the given pipeline was built with another tta than run_test is asked for")
     tta = loader.pipeline.tta
     model.eval()
-    if store is None:
+    if world > 1:
+        # this rank's contiguous shard into a store of the common capacity (q scenes, worst-case rows: known from
+        # the model's configuration, so an empty shard allocates it too), then the ranks' stores merged in rank
+        # order = dataset order, on every rank
+        if store is not None:
+            raise ValueError("run_test under ranks returns the merged store: it does not take one to append to")
+        n = len(dataset)
+        q = -(-n // world)
+        counts = [max(0, min(n, (r + 1) * q) - r * q) for r in range(world)]
+        cap = max(q, 1)
+        store = DetectionStore(cap, max_rows=cap * ranks.rows_per_scene(model, tta), device=loader.device)
+    elif store is None:
         store = DetectionStore(max(len(dataset), 1), device=loader.device)
     if tta is None:
         for batch in loader:
             model.predict_into(store, **batch)
-        return store
-    view_store = DetectionStore(tta.num_views * int(batch_size), device=loader.device)
-    for batch in loader:
-        model.aug_predict_into(store, **batch, tta=tta, view_store=view_store)
-    return store
+    else:
+        view_store = DetectionStore(tta.num_views * int(batch_size), device=loader.device)
+        for batch in loader:
+            model.aug_predict_into(store, **batch, tta=tta, view_store=view_store)
+    return ranks.merge_stores(store, counts) if world > 1 else store
 
 
 def _model_state(ckpt):
@@ -100,9 +124,14 @@ def parse_args(argv=None):
                    help="overlap of the merging NMS: rotated BEV (default), rotated 3-D, axis-aligned BEV")
     p.add_argument("--tta-nms-thr", type=float, default=None,
                    help="IoU threshold of the merging NMS (default: the head's test_cfg nms_thr)")
+    p.add_argument("--gpus", type=int, default=None,
+                   help="run as N ranks, one GPU each (started here unless a launcher already set RANK); "
+                        "--workers is per rank")
     args = p.parse_args(argv)
     if args.batch_size < 1 or args.workers < 1:
         p.error("--batch-size and --workers must be positive")
+    if args.gpus is not None and args.gpus < 1:
+        p.error("--gpus must be positive")
     args.tta = None
     if args.tta_scales is not None or args.tta_flip:
         from .tta import TTACfg
@@ -127,6 +156,14 @@ def main(argv=None, model=None, **loader_kwargs):
     detector to use instead of the full-size ``DeMFVoteNet()``; ``loader_kwargs`` go to ``run_test``
     (``num_points``, ``img_scale``, ``seed``)."""
     args = parse_args(argv)
+    if "RANK" in os.environ:
+        from . import engine
+        ranks.check_gpus(args.gpus)
+        engine.init_distributed()
+    elif args.gpus is not None and args.gpus > 1:
+        if model is not None or loader_kwargs:
+            raise ValueError("--gpus starts new processes: a model or loader arguments given in this one cannot follow")
+        return ranks.launch("demf_amd.infer", sys.argv[1:] if argv is None else list(argv), args.gpus)
     from .dataset import RGBDFrames, SUNRGBDDataset
     if args.frames:
         from .pipeline import FramePipeline
@@ -143,6 +180,8 @@ def main(argv=None, model=None, **loader_kwargs):
     model.cuda()
     store = run_test(model, dataset, batch_size=args.batch_size, workers=args.workers, tta=args.tta,
                      **loader_kwargs)
+    if ranks.rank() != 0:                       # (the merged store is on every rank; rank 0 alone reports)
+        return None
     if args.out:
         with open(args.out, "wb") as f:
             pickle.dump(store.results(), f)
@@ -154,4 +193,5 @@ def main(argv=None, model=None, **loader_kwargs):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    _ret = main(sys.argv[1:])
+    sys.exit(_ret if isinstance(_ret, int) else 0)

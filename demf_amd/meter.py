@@ -86,10 +86,14 @@ class StepMeter:
         ops.step_meter(list(scalars), opt_state, grad_scale, max_norm, self.ring)
 
     def snapshot(self):
-        """Enqueue one device -> pinned copy of the ring and an event behind it; does not wait."""
+        """Enqueue one device -> pinned copy of the ring and an event behind it; does not wait.  In a process group
+        of more than one rank the ring copied is the merge of every rank's (``ranks.merge_rings``: one collective of
+        ``rows * 64`` bytes per rank, then ``ops.meter_merge`` on the current stream), so every rank decodes the same
+        rows - the loss terms averaged over ranks; every rank has to take its snapshots at the same steps."""
+        from . import ranks
         buf = self._free.pop() if self._free else torch.empty((self.rows, ROW_WORDS), dtype=torch.int32,
                                                               pin_memory=True)
-        buf.copy_(self.ring, non_blocking=True)
+        buf.copy_(ranks.merge_rings(self.ring) if ranks.world() > 1 else self.ring, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         self._pending.append((buf, ev))

@@ -2615,3 +2615,59 @@ def scalars_accum(scalars, acc, scale):
         raise ValueError("scalars_accum: the accumulator holds %d floats, %d scalars given" % (acc.numel(), len(scalars)))
     tab = (ctypes.c_void_p * len(scalars))(*[s.data_ptr() for s in scalars])
     _ffi.call("demf_scalars_accum", len(scalars), ctypes.addressof(tab), _p(acc), float(scale), _stream())
+
+
+# --------------------------------------------------------------------------
+# Rank merges (csrc/ranks.hip; ranks.py puts the collective in front)
+# --------------------------------------------------------------------------
+RANKS_MAX = 64                    # W of store_concat / meter_merge
+
+
+def store_concat(counts, scene_off, state, boxes, scores, labels, out_boxes, out_scores, out_labels, out_scene_off,
+                 out_state):
+    """The ``DetectionStore`` arrays of W ranks, stacked rank-major - ``scene_off`` (W, S+1), ``state`` (W, 2),
+    ``boxes`` (W, R, 7), ``scores`` (W, R), ``labels`` (W, R) - concatenated in rank order into the arrays of one
+    destination store (demf_store_concat).  ``counts``: the scenes each rank appended, HOST ints.  Nothing is
+    returned and nothing is synchronised: the row counts stay on the device."""
+    counts = [int(c) for c in counts]
+    W = len(counts)
+    _chk(scene_off, "scene_off", torch.int32)
+    _chk(state, "state", torch.int32)
+    _chk(boxes, "boxes")
+    _chk(scores, "scores")
+    _chk(labels, "labels", torch.int32)
+    _chk(out_boxes, "out_boxes")
+    _chk(out_scores, "out_scores")
+    _chk(out_labels, "out_labels", torch.int32)
+    _chk(out_scene_off, "out_scene_off", torch.int32)
+    _chk(out_state, "out_state", torch.int32)
+    if W < 1 or scene_off.dim() != 2 or scene_off.shape[0] != W or scene_off.shape[1] < 2:
+        raise ValueError("store_concat: scene_off must be (W, S + 1) for the W = %d counts given" % W)
+    R = scores.shape[1] if scores.dim() == 2 else -1
+    if tuple(state.shape) != (W, 2) or tuple(boxes.shape) != (W, R, 7) or tuple(scores.shape) != (W, R) or \
+            tuple(labels.shape) != (W, R):
+        raise ValueError("store_concat: state (W, 2), boxes (W, R, 7), scores (W, R) and labels (W, R) expected")
+    max_rows = out_scores.numel()
+    if out_boxes.numel() != 7 * max_rows or out_labels.numel() != max_rows or out_state.numel() != 2 or \
+            out_scene_off.numel() < 2:
+        raise ValueError("store_concat: the destination arrays are not those of one DetectionStore")
+    tab = (ctypes.c_int * W)(*counts)
+    _ffi.call("demf_store_concat", W, ctypes.addressof(tab), scene_off.shape[1] - 1, R, _p(scene_off), _p(state),
+              _p(boxes), _p(scores), _p(labels), out_scene_off.numel() - 1, max_rows, _p(out_boxes), _p(out_scores),
+              _p(out_labels), _p(out_scene_off), _p(out_state), _stream())
+
+
+def meter_merge(rings, out=None):
+    """W step-meter rings (W, rows, 16) int32 -> one ring (rows, 16) whose scalars are the mean over ranks (fp64 sum
+    in ascending rank order), flags OR'd, head words rank 0's; a row whose stamps differ between ranks becomes an
+    empty-ring row (demf_meter_merge).  -> ``out`` (a new tensor when None)."""
+    _chk(rings, "rings", torch.int32)
+    if rings.dim() != 3 or rings.shape[2] != METER_ROW_WORDS or rings.shape[0] < 1 or rings.shape[1] < 1:
+        raise ValueError("meter_merge: rings must be (W >= 1, rows >= 1, %d) int32" % METER_ROW_WORDS)
+    if out is None:
+        out = torch.empty(rings.shape[1:], dtype=torch.int32, device=rings.device)
+    _chk(out, "out", torch.int32)
+    if tuple(out.shape) != tuple(rings.shape[1:]):
+        raise ValueError("meter_merge: out must be (rows, %d) int32" % METER_ROW_WORDS)
+    _ffi.call("demf_meter_merge", int(rings.shape[0]), int(rings.shape[1]), _p(rings), _p(out), _stream())
+    return out

@@ -395,6 +395,39 @@ class SceneBatch(dict):
         return self
 
 
+def shard_chunks(order, batch_size, rank=0, world=1, mode="train", drop_last=False):
+    """The index arrays rank ``rank`` of ``world`` iterates over ``order`` (an epoch's scene order), as a list.
+
+    ``world == 1``: ``order`` cut into chunks of ``batch_size``; the short last one is kept unless ``drop_last``.
+    Train mode, ``world > 1``: ``order`` (the permutation a single process draws) is extended by wrap-around to a
+    multiple of ``world * batch_size`` (``drop_last``: cut down to one), cut into chunks of ``batch_size``, and rank r
+    takes chunks r, r + W, r + 2W, ...: every rank runs the same number of full batches, and optimizer step k of the
+    W ranks consumes the chunks a single process with ``accumulate = W`` consumes in its group k.
+    Test mode, ``world > 1``: contiguous shards, rank r takes ``order[r * q : (r + 1) * q]`` with q = ceil(n / W),
+    chunked by ``batch_size``; a shard may be empty."""
+    order = np.asarray(order)
+    bs, rank, world = int(batch_size), int(rank), int(world)
+    if bs < 1 or world < 1 or not 0 <= rank < world:
+        raise ValueError(f"shard_chunks: batch_size {bs}, rank {rank} of {world}")
+    if mode not in ("train", "test"):
+        raise ValueError(f"mode must be 'train' or 'test', got {mode!r}")
+    n = len(order)
+    if world > 1 and mode == "train":
+        group = world * bs
+        total = n // group * group if drop_last else -(-n // group) * group
+        if n == 0 or total == 0:
+            return []
+        ext = order[np.arange(total) % n]
+        return [ext[i:i + bs] for i in range(rank * bs, total, group)]
+    if world > 1:
+        q = -(-n // world)
+        order = order[rank * q:min(n, (rank + 1) * q)]
+    chunks = [order[i:i + bs] for i in range(0, len(order), bs)]
+    if drop_last and chunks and len(chunks[-1]) < bs:
+        chunks.pop()
+    return chunks
+
+
 class SceneLoader:
     """Batches of a dataset through ``ScenePipeline`` with host reads in ``workers`` threads and the device work on
     the loader's own stream, one batch ahead: while the consumer runs step k, batch k+1's kernels are queued on the
@@ -407,10 +440,17 @@ class SceneLoader:
 
     ``pipeline``: an instance (e.g. ``FramePipeline`` over ``RGBDFrames``) to use in place of the ``ScenePipeline``
     the loader would build; it then brings its own ``img_scale`` / ``num_points`` / ``seed``, and ``mode`` defaults
-    to its mode (``"train"`` otherwise)."""
+    to its mode (``"train"`` otherwise).
+
+    ``rank`` / ``world``: the loader yields this rank's share of every epoch (``shard_chunks``); the permutation and
+    the augmentations stay keyed on (seed, epoch[, index]), so a scene looks the same whichever rank draws it."""
 
     def __init__(self, dataset, batch_size, mode=None, seed=0, img_scale=(1333, 800), num_points=20000,
-                 workers=8, drop_last=False, device=None, pipeline=None, with_img=None, image_shapes=None, tta=None):
+                 workers=8, drop_last=False, device=None, pipeline=None, with_img=None, image_shapes=None, tta=None,
+                 rank=0, world=1):
+        if int(world) < 1 or not 0 <= int(rank) < int(world):
+            raise ValueError(f"rank {rank} of world {world}")
+        self.rank, self.world = int(rank), int(world)
         if tta is not None and pipeline is not None:
             raise ValueError("tta belongs to the pipeline the loader builds; the given pipeline brings its own")
         if mode is None:
@@ -435,6 +475,8 @@ class SceneLoader:
 
     def __len__(self):
         n = len(self.dataset)
+        if self.world > 1:
+            return len(shard_chunks(np.arange(n), self.batch_size, self.rank, self.world, self.mode, self.drop_last))
         return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
 
     def _order(self, epoch):
@@ -463,10 +505,7 @@ class SceneLoader:
         if self._stream is None:
             self._stream = torch.cuda.Stream(self.device)
         order = self._order(epoch)
-        bs = self.batch_size
-        chunks = [order[i:i + bs] for i in range(0, len(order), bs)]
-        if self.drop_last and chunks and len(chunks[-1]) < bs:
-            chunks.pop()
+        chunks = shard_chunks(order, self.batch_size, self.rank, self.world, self.mode, self.drop_last)
         if not chunks:
             return
         pool = ThreadPoolExecutor(max_workers=max(1, self.workers))

@@ -4,7 +4,7 @@
                            [--val-ann-file sunrgbd_infos_val.pkl] [--load-from C] [--resume-from C] [--no-validate]
                            [--no-graphs] [--batch-size 16] [--epochs 36] [--seed 0] [--workers 4] [--log-interval 50]
                            [--accumulate 1] [--autoscale-lr] [--model {demf,votenet}]
-                           [--feature-cache DIR [--feature-cache-dtype {fp32,bf16}]]
+                           [--feature-cache DIR [--feature-cache-dtype {fp32,bf16}]] [--gpus N]
 
 ``fit`` feeds a dataset through ``SceneLoader(mode="train")``, the frozen image stream and ``engine.Trainer`` (one
 captured hipGraph per batch shape, ``StepCache``).  Losses, gradient norm and learning rate are logged through the
@@ -13,9 +13,18 @@ never waits for the GPU between log points.  Checkpoints are written per epoch, 
 a layout ``infer.load_checkpoint`` and the reference's tools read; ``resume_from`` continues with the next epoch
 (mmcv's resume granularity).  Validation is ``infer.run_test`` + ``dataset.evaluate``.
 
-Single process, one GPU.  Multi-rank training (the reference's tools/dist_train.sh) is not part of this module;
-``--accumulate 8`` forms the step of its 8 ranks x 16 scenes from 8 forward + backward passes instead (gradient
-accumulation, ``engine.Trainer(accumulate=W)``): iterations, log lines and the meter then count OPTIMIZER steps.
+``--accumulate 8`` forms the step of the reference's 8 ranks x 16 scenes from 8 forward + backward passes on one GPU
+(gradient accumulation, ``engine.Trainer(accumulate=W)``): iterations, log lines and the meter then count OPTIMIZER
+steps.
+
+``--gpus N`` is the reference's tools/dist_train.sh: N ranks of this module, one GPU each (``ranks.launch``; under a
+launcher that set ``RANK``, ``main`` joins the process group instead).  ``fit`` then gives every rank its share of
+each epoch's permutation (``pipeline.shard_chunks``: optimizer step k consumes the chunks a single process with
+``accumulate = N`` consumes in its group k), ``engine.Trainer`` keeps the replicas identical (rank-0 broadcast, SUM
+all-reduce of the flat gradient buffer), the log's loss terms are the mean over ranks (``StepMeter.snapshot`` merges
+the ranks' rings), rank 0 alone writes ``train.log.json`` and the checkpoints, and validation runs sharded
+(``infer.run_test``) after rank 0's BatchNorm statistics have been broadcast.  Without a process group nothing of
+this runs: single process, one GPU, the files and log lines of before.
 """
 import argparse
 import functools
@@ -81,6 +90,16 @@ def check_resume_accumulate(meta, accumulate, path="the checkpoint"):
     if was != int(accumulate):
         raise ValueError("resume_from %s was trained with accumulate = %d, this run asks for accumulate = %d"
                          % (path, was, int(accumulate)))
+    return was
+
+
+def check_resume_world(meta, world, path="the checkpoint"):
+    """A resumed run keeps the checkpoint's ``world`` (the ranks' shards and the number of iterations per epoch
+    depend on it); the field is written only when it is above 1, and an absent one reads as 1."""
+    was = int(meta.get("world", 1))
+    if was != int(world):
+        raise ValueError("resume_from %s was trained with world = %d ranks, this run has world = %d"
+                         % (path, was, int(world)))
     return was
 
 
@@ -189,11 +208,15 @@ def _lookahead(it):
 
 
 class _Log:
+    """``path`` None: a rank that keeps no log (every rank but 0) - lines are dropped."""
+
     def __init__(self, path, echo=True):
-        self.f = open(path, "a")
+        self.f = None if path is None else open(path, "a")
         self.echo = echo
 
     def write(self, line):
+        if self.f is None:
+            return
         text = json.dumps(line)
         self.f.write(text + "\n")
         self.f.flush()
@@ -201,7 +224,8 @@ class _Log:
             print(text, flush=True)
 
     def close(self):
-        self.f.close()
+        if self.f is not None:
+            self.f.close()
 
 
 def model_loss_names(model):
@@ -215,12 +239,15 @@ def model_loss_names(model):
 
 def validate(model, val_set, batch_size, workers, num_points, img_scale, seed=0):
     """One validation pass: ``infer.run_test`` into a fresh store, ``val_set.evaluate``; the model goes back to
-    ``train()`` (for ``DeMFVoteNet`` that keeps the image branch in eval)."""
-    from . import infer
+    ``train()`` (for ``DeMFVoteNet`` that keeps the image branch in eval).  Under ranks: rank 0's buffers (the
+    BatchNorm statistics, which every rank has updated from its own batches) go to every rank first, the pass runs
+    sharded, rank 0 evaluates the merged store and its dict is broadcast - every rank returns the same."""
+    from . import infer, ranks
     try:
+        ranks.broadcast_buffers(model)
         store = infer.run_test(model, val_set, batch_size=batch_size, workers=workers, num_points=num_points,
                                img_scale=img_scale, seed=seed)
-        return val_set.evaluate(store)
+        return ranks.broadcast_object(val_set.evaluate(store) if ranks.rank() == 0 else None)
     finally:
         model.train()
 
@@ -250,8 +277,12 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
     ``feature_cache`` (a ``featcache.FeatureCache`` of ``train_set`` for this model's image branch): the loader opens
     no image file (``SceneLoader(with_img=False, image_shapes=cache.ori_shapes)``) and every batch's image features
     are ``feature_cache.assemble(batch.indices, batch["img_metas"])``; ``model.extract_img_feat`` is not called in
-    the training loop.  Validation still computes the stream: a validation scene is seen once per pass."""
-    from . import engine, infer
+    the training loop.  Validation still computes the stream: a validation scene is seen once per pass.
+
+    In a process group of W > 1 ranks (``engine.init_distributed``) this is one rank of a data-parallel run: the
+    loader yields the rank's share, ``on_step`` sees the rank's indices, every rank returns the same ``val``, and the
+    log and the checkpoints are rank 0's (module docstring)."""
+    from . import engine, infer, ranks
     from .meter import StepMeter
     from .modules import DeMFHotPath
     from .pipeline import SceneLoader
@@ -268,14 +299,15 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
         if tuple(feature_cache.img_scale) != tuple(img_scale):
             raise ValueError("feature_cache holds img_scale %s, the run asks for %s"
                              % (tuple(feature_cache.img_scale), tuple(img_scale)))
+    world, rank = ranks.world(), ranks.rank()
     os.makedirs(work_dir, exist_ok=True)
-    torch.manual_seed(seed)                       # (the Trainer seeds the dropout counter from it)
+    torch.manual_seed(seed)                       # (the Trainer seeds the dropout counter from it and from the rank)
     model.cuda().train()
     if load_from is not None:
         # weights only (mmcv's load_from): through the model's load_state_dict, which for DeMFVoteNet applies the
         # stage-1 image-branch key remap; a stage-1 file holds the image branch alone, so not strict
         bad = model.load_state_dict(infer._model_state(load_checkpoint_file(load_from)), strict=False)
-        if echo:
+        if echo and rank == 0:
             print(f"load_from {load_from}: {len(bad.missing_keys)} missing, {len(bad.unexpected_keys)} unexpected keys",
                   flush=True)
     # the runner computes the frozen image features itself and drives the hot path's forward_train
@@ -289,16 +321,25 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
     if resume_from is not None:
         ckpt = load_checkpoint_file(resume_from)
         check_resume_accumulate(ckpt["meta"], accumulate, resume_from)
+        check_resume_world(ckpt["meta"], world, resume_from)
         meta = restore_checkpoint(ckpt, model, trainer, meter)
         epoch0, it = int(meta["epoch"]), int(meta["iter"])
+        if rank > 0 and trainer.fused:
+            # the file holds rank 0's dropout counter [seed, step]: this rank keeps its own seed (engine.Trainer:
+            # seed + 7919 * rank) at the checkpoint's step
+            from . import fused
+            dev = trainer.flat.flat.device
+            s0, k0 = fused.get_rng_state(dev)
+            fused.set_rng_state(dev, [(s0 + 7919 * rank) & 0x7FFFFFFFFFFFFFFF, k0])
     if feature_cache is not None and (load_from is not None or resume_from is not None):
         feature_cache.verify()                    # (the weights just loaded must be the ones the cache was built from)
     stepper = trainer.bucketed() if graphs else None
     loader = SceneLoader(train_set, batch_size, "train", seed=seed, img_scale=img_scale, num_points=num_points,
                          workers=workers, with_img=with_img and feature_cache is None,
-                         image_shapes=None if feature_cache is None else feature_cache.ori_shapes)
+                         image_shapes=None if feature_cache is None else feature_cache.ori_shapes,
+                         rank=rank, world=world)
     ipe, dropped = accumulation_plan(len(loader), repeat, accumulate)      # iterations per runner epoch
-    log = _Log(os.path.join(work_dir, "train.log.json"), echo)
+    log = _Log(os.path.join(work_dir, "train.log.json") if rank == 0 else None, echo)
     rows, marks = [], []                          # meter rows not logged yet; (last t, epoch, iter, s/iter) per interval
 
     def drain(wait):
@@ -321,6 +362,8 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
             def mark():
                 nonlocal since, t_mark
                 now = time.perf_counter()
+                if world > 1:
+                    trainer.flush()               # (an overlapped collective's update, and its meter row, are owed)
                 meter.snapshot()
                 # (with accumulate > 1 the epoch's last line says how many batches its open group loses)
                 extra = dict(discarded=dropped) if accumulate > 1 and it == it_end else {}
@@ -363,7 +406,11 @@ def fit(model, train_set, work_dir, *, val_set=None, batch_size=DEFAULTS["batch_
                 meta = dict(epoch=done, iter=it, seed=int(seed), repeat=int(repeat), batch_size=int(batch_size),
                             lr=float(lr), lr_steps=[int(s) for s in lr_steps], gamma=float(gamma),
                             max_epochs=int(max_epochs), accumulate=int(accumulate))
-                save_checkpoint(work_dir, done, make_checkpoint(model, trainer, meter, meta), max_keep_ckpts)
+                if world > 1:
+                    meta["world"] = int(world)
+                if rank == 0:
+                    save_checkpoint(work_dir, done, make_checkpoint(model, trainer, meter, meta), max_keep_ckpts)
+                ranks.barrier()                   # (no rank runs ahead of a file another run may resume from)
             if val_set is not None and (done % eval_interval == 0 or done == max_epochs):
                 trainer.flush()
                 val = validate(model, val_set, val_batch_size or batch_size, workers, num_points, img_scale, seed)
@@ -387,12 +434,16 @@ def parse_args(argv=None):
     p.add_argument("--batch-size", type=int, default=DEFAULTS["batch_size"])
     p.add_argument("--epochs", type=int, default=DEFAULTS["max_epochs"])
     p.add_argument("--seed", type=int, default=DEFAULTS["seed"])
-    p.add_argument("--workers", type=int, default=DEFAULTS["workers"])
+    p.add_argument("--workers", type=int, default=DEFAULTS["workers"],
+                   help="loader threads PER PROCESS: with --gpus N the job runs N times as many (a job that is given "
+                        "16 CPUs in all has 2 per rank at N = 8)")
+    p.add_argument("--gpus", type=int, default=None,
+                   help="run as N data-parallel ranks, one GPU each (started here unless a launcher already set RANK)")
     p.add_argument("--log-interval", type=int, default=DEFAULTS["log_interval"])
     p.add_argument("--accumulate", type=int, default=DEFAULTS["accumulate"],
                    help="batches per optimizer step (8: the reference's 8-GPU step on one GPU)")
     p.add_argument("--autoscale-lr", action="store_true",
-                   help="the reference's linear scaling rule: lr x accumulate / 8")
+                   help="the reference's linear scaling rule: lr x (accumulate x ranks) / 8")
     p.add_argument("--model", choices=("demf", "votenet"), default="demf",
                    help="demf: DeMFVoteNet (configs/demf/demf_votenet.py); votenet: the points-only class-agnostic "
                         "baseline (configs/baseline/votenet.py), trained without reading an image")
@@ -410,6 +461,8 @@ def parse_args(argv=None):
         p.error("--batch-size, --workers, --log-interval and --accumulate must be positive")
     if args.epochs < 0:
         p.error("--epochs must not be negative")
+    if args.gpus is not None and args.gpus < 1:
+        p.error("--gpus must be positive")
     if args.load_from and args.resume_from:
         p.error("--load-from and --resume-from exclude each other (a resumed run takes its weights from the checkpoint)")
     return args
@@ -450,6 +503,15 @@ def main(argv=None, model=None, **fit_kwargs):
     """-> what ``fit`` returns.  ``model``: the detector to train instead of the full-size ``DeMFVoteNet()``;
     ``fit_kwargs`` go to ``fit`` (``num_points``, ``img_scale``, schedule overrides, ``on_step``)."""
     args = parse_args(argv)
+    from . import ranks
+    if "RANK" in os.environ:
+        from . import engine
+        ranks.check_gpus(args.gpus)
+        engine.init_distributed()
+    elif args.gpus is not None and args.gpus > 1:
+        if model is not None or fit_kwargs:
+            raise ValueError("--gpus starts new processes: a model or fit arguments given in this one cannot follow")
+        return ranks.launch("demf_amd.train", sys.argv[1:] if argv is None else list(argv), args.gpus)
     from .dataset import SUNRGBDDataset
     train_set = SUNRGBDDataset(args.data_root, args.ann_file)
     val_set = None
@@ -462,14 +524,26 @@ def main(argv=None, model=None, **fit_kwargs):
               workers=args.workers, log_interval=args.log_interval, graphs=not args.no_graphs,
               resume_from=args.resume_from, load_from=args.load_from, accumulate=args.accumulate)
     if args.autoscale_lr:
-        kw["lr"] = autoscale_lr(DEFAULTS["lr"], args.accumulate)
+        kw["lr"] = autoscale_lr(DEFAULTS["lr"], args.accumulate, ranks.world())
     kw.update(fit_kwargs)
     if args.feature_cache is not None:
-        kw["feature_cache"] = open_feature_cache(args.feature_cache, model, train_set, args.feature_cache_dtype,
-                                                 load_from=kw.get("load_from"), resume_from=kw.get("resume_from"),
-                                                 img_scale=kw.get("img_scale", (1333, 800)))
+        # rank 0 opens first, building and saving the cache if it has to; the others load what it left (every rank
+        # holds the whole cache: the permutation is global)
+        opened = functools.partial(open_feature_cache, args.feature_cache, model, train_set, args.feature_cache_dtype,
+                                   load_from=kw.get("load_from"), resume_from=kw.get("resume_from"),
+                                   img_scale=kw.get("img_scale", (1333, 800)))
+        if ranks.world() > 1:
+            # (without --load-from / --resume-from every rank has drawn its own weights: the cache is a function of
+            # the image branch, so the replicas are made identical here already, not only by the Trainer)
+            ranks.broadcast_buffers(model.cuda(), parameters=True)
+        if ranks.rank() == 0:
+            kw["feature_cache"] = opened()
+        ranks.barrier()
+        if ranks.rank() != 0:
+            kw["feature_cache"] = opened(echo=False)
     return fit(model, train_set, args.work_dir, **kw)
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    _ret = main(sys.argv[1:])
+    sys.exit(_ret if isinstance(_ret, int) else 0)

@@ -1081,6 +1081,35 @@ DEMF_INTERNAL int demf_scalars_accum(int n, const float* const* scalars, float* 
                        demf_stream_t stream);
 
 /* ------------------------------------------------------------------ *
+ * Rank merges (csrc/ranks.hip): the device state of W data-parallel ranks, ALREADY GATHERED into rank-major
+ * device arrays, merged into one.  No communication in here; W > 64 returns DEMF_EUNSUPPORTED.
+ * ------------------------------------------------------------------ */
+
+/* W DetectionStores -> one, in rank order.  counts: HOST array of W ints, n_r = the scenes rank r appended
+ * (0 <= n_r <= S, sum <= max_scenes).  Sources, DEVICE, the ranks' arrays stacked: src_scene_off (W, S+1),
+ * src_state (W, 2), src_boxes (W, R, 7), src_scores (W, R), src_labels (W, R); S / R = the common per-rank scene /
+ * row capacity.  Destination: the arrays of a store of max_scenes scenes and max_rows rows.
+ *   rows_r = max(src_scene_off[r][n_r], 0)  - it keeps counting past R when rank r overflowed
+ *   base_r = sum of rows_q over q < r (64-bit);  global scene g = sum of n_q over q < r, + i
+ *   scene_off[g] = base_r + src_scene_off[r][i];  scene_off[sum n_r] = state[0] = sum rows_r
+ *   state[1] = 1 if any src_state[r][1] != 0 or sum rows_r > max_rows (a row index reaches max_rows), else 0
+ *   row j < min(rows_r, R) of rank r is copied bit for bit to row base_r + j when base_r + j < max_rows
+ * (demf_detect_pack's rule: rows that do not fit are counted, not written).  Nothing else is written: neither
+ * scene_off beyond sum n_r nor a row at or beyond sum rows_r.  One launch sized for R full rows per rank; the
+ * row counts are read on the device, no host sync.  Vector stores only, one writer per word.                 */
+DEMF_INTERNAL int demf_store_concat(int W, const int* counts, int S, int R, const int* src_scene_off,
+                      const int* src_state, const float* src_boxes, const float* src_scores,
+                      const int* src_labels, int max_scenes, int max_rows, float* boxes, float* scores,
+                      int* labels, int* scene_off, int* state, demf_stream_t stream);
+
+/* W step-meter rings (W, rows, 16) words in demf_step_meter's row layout -> out (rows, 16).  A row whose int64
+ * stamp is the same on every rank: stamp kept; flags = OR over ranks; words 3-5 (lr_factor, grad_norm, clip) rank
+ * 0's; each of the ten scalars (float)(sum over r of (double)x_r, ascending r, then / W) - non-finite values
+ * propagate.  A row whose stamps differ is written as the row of an empty ring (stamp -1, other words 0).
+ * W == 1 copies bit for bit.                                                                              */
+DEMF_INTERNAL int demf_meter_merge(int W, int rows, const void* rings, void* out, demf_stream_t stream);
+
+/* ------------------------------------------------------------------ *
  * Dense blocks of the DeMF fusion decoder layer (csrc/dense.hip)
  * Reference: demf/modeling/layers/transformer.py:55-80 -> mmcv DetrTransformerDecoderLayer
  * (nn.MultiheadAttention, MultiScaleDeformableAttention, FFN, 3 x LayerNorm; cfg
