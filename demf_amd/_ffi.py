@@ -1,214 +1,98 @@
-"""ctypes binding of libdemf_hip.so (the C ABI declared in include/demf_hip.h).
+"""ctypes binding of libdemf_hip.so, derived from the C ABI declared in include/demf_hip.h.
 
-The reference reaches its native operators through pybind extensions of
-mmdet3d/mmcv; this is the equivalent thin layer.  cffi is not installed in the
-target image, so the binding is ctypes.  There is no fallback: if the library is
-missing, ``load()`` raises.
+The reference reaches its native operators through pybind extensions of mmdet3d/mmcv; this is the equivalent thin
+layer.  cffi is not installed in the target image, so the binding is ctypes.  There is no fallback: if the library
+is missing, ``load()`` raises.
+
+The header is the one source: every ``.hip`` includes it, so a definition that disagrees with its prototype
+does not compile, and the argument types, structs and constants below are read from it at import.  A
+declaration the parser does not know raises; it never guesses.
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DEMF_LIB_PATH") or os.path.join(_HERE, "lib", "libdemf_hip.so")     # (A/B builds)
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "demf_hip.h")
 
-_c_int = ctypes.c_int
-_c_float = ctypes.c_float
-_ptr = ctypes.c_void_p
-
-# name -> argtypes, exactly mirroring include/demf_hip.h
-SIGNATURES = {
-    "demf_stream_create_cu_masked": [_ptr, _c_int, _c_int, _ptr],
-    "demf_spin_us": [_c_int, _ptr],
-    "demf_conv_nhwc_f32": [_c_int] * 9 + [_ptr, _ptr, _c_int, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr],
-    "demf_conv_stem7_nhwc4_f32": [_c_int] * 4 + [_ptr, _ptr, _c_int, _ptr, _c_int, _ptr, _ptr],
-    "demf_maxpool3x3s2_nhwc_f32": [_c_int] * 4 + [_ptr, _ptr, _ptr],
-    "demf_nchw3_to_nhwc4_f32": [_c_int] * 3 + [_ptr, _ptr, _ptr],
-    "demf_groupnorm_nhwc_f32": [_c_int] * 4 + [_c_float, _ptr, _ptr, _ptr, _ptr, _ptr, ctypes.c_longlong, _ptr],
-    "demf_fps_f32": [_c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr],
-    "demf_fps_ws_f32": [_c_int, _c_int, _c_int, _ptr, _ptr, ctypes.c_longlong, _ptr, _ptr],
-    "demf_ball_query_f32": [_c_int, _c_int, _c_int, _c_float, _c_float, _c_int, _ptr, _ptr,
-                            _ptr, _ptr],
-    "demf_ball_query_grid_ws": [_c_int, _c_int, _ptr, _ptr],
-    "demf_ball_query_grid_f32": [_c_int, _c_int, _c_int, _c_float, _c_int] + [_ptr] * 6,
-    "demf_group_points_fwd": [_c_int] * 5 + [_ptr] * 4,
-    "demf_group_points_bwd": [_c_int] * 5 + [_ptr] * 4,
-    "demf_gather_points_fwd": [_c_int] * 4 + [_ptr] * 4,
-    "demf_gather_points_bwd": [_c_int] * 4 + [_ptr] * 4,
-    "demf_three_nn_f32": [_c_int] * 3 + [_ptr] * 5,
-    "demf_three_nn_weights_f32": [_c_int] * 3 + [_ptr] * 6,
-    "demf_three_interpolate_fwd": [_c_int] * 4 + [_ptr] * 5,
-    "demf_three_interpolate_bwd": [_c_int] * 4 + [_ptr] * 5,
-    "demf_group_concat_cl_fwd": [_c_int] * 8 + [_c_float, _c_int] + [_ptr] * 6,
-    "demf_group_concat_cl_bwd": [_c_int] * 8 + [_c_float, _c_int] + [_ptr] * 6,
-    "demf_gather_rows_cl_fwd": [_c_int] * 4 + [_ptr] * 4,
-    "demf_gather_rows_cl_bwd": [_c_int] * 4 + [_ptr] * 4,
-    "demf_three_interpolate_cl_fwd": [_c_int] * 6 + [_ptr] * 5,
-    "demf_three_interpolate_cl_bwd": [_c_int] * 6 + [_ptr] * 5,
-    "demf_three_interpolate_cat_cl_fwd": [_c_int] * 5 + [_ptr] * 6,
-    "demf_maxpool_ns_fwd": [_c_int] * 3 + [_ptr] * 4,
-    "demf_maxpool_ns_bwd": [_c_int] * 3 + [_ptr] * 4,
-    "demf_colsum_f32": [_c_int] * 3 + [_ptr] * 3,
-    "demf_nchw_to_tokens": [_c_int] * 5 + [_ptr] * 4,
-    "demf_pyramid_to_tokens": [_c_int] * 4 + [_ptr] * 5,
-    "demf_pyramid_to_tokens_bf16": [_c_int] * 4 + [_ptr] * 5,
-    "demf_tokens_assemble": [_c_int] * 4 + [ctypes.c_longlong] * 2 + [_ptr, _c_int] + [_ptr] * 7 + [_c_int, _ptr],
-    "demf_vote_targets": [_c_int] * 4 + [_ptr] * 8,
-    "demf_box_extent_count": [_c_int] * 4 + [_ptr] * 8,
-    "demf_aligned_nms": [_c_int, _c_int, _c_float] + [_ptr] * 6,
-    "demf_detect_decode": [_c_int] * 6 + [_ptr] * 7 + [_ptr],
-    "demf_ca_detect_decode": [_c_int] * 5 + [_ptr, _c_int, _c_int] * 3 + [_ptr] * 6 + [_ptr],
-    "demf_detect_pack": [_c_int] * 4 + [_c_float] + [_ptr] * 5 + [_c_int] * 3 + [_ptr] * 5 + [_ptr],
-    "demf_box3d_iou": [_c_int, _c_int] + [_ptr] * 4,
-    "demf_eval_match": [_c_int, _c_int, _ptr, _c_int, _c_int] + [_ptr] * 7,
-    "demf_eval_ap": [_c_int, _c_int] + [_ptr] * 8,
-    "demf_nms_bev": [_c_int] * 3 + [_c_float, _c_int] + [_ptr] * 7 + [_ptr],
-    "demf_tta_merge": [_c_int] * 4 + [_c_float, _c_int, _c_int] + [_ptr] * 5 + [_c_int] * 3 + [_ptr] * 5 +
-                      [_c_int] * 3 + [_ptr] * 5 + [_ptr],
-    "demf_points_floor": [_c_int, _c_int, ctypes.c_longlong] + [_ptr] * 4,
-    "demf_points_prep": [_c_int] * 3 + [ctypes.c_longlong] + [_ptr] * 8,
-    "demf_image_prep": [_c_int] * 3 + [ctypes.c_longlong] + [_ptr] * 6,
-    "demf_depth_to_points": [_c_int, ctypes.c_longlong, ctypes.c_longlong, _c_int] + [_ptr] * 6 + [_c_int] + [_ptr] * 4,
-    "demf_proposal_targets": [_c_int] * 4 + [_c_float] * 3 + [_ptr] * 18,
-    "demf_gt_prep": [_c_int] * 3 + [_ptr] * 10,
-    "demf_pad_gt": [_c_int] * 2 + [_ptr] * 8,
-    "demf_query_pos_rows": [_c_int] * 2 + [_ptr] * 4,
-    "demf_loss_total": [_c_int] + [_ptr] * 4,
-    "demf_loss_total_bwd": [_c_int] + [_ptr] * 4,
-    "demf_target_weights": [_c_int] + [_ptr] * 5,
-    "demf_rows_ln_pos_f32": [_c_int] * 2 + [_ptr] * 4 + [_c_float] + [_ptr] * 4,
-    "demf_rows_gemm_f32": [_c_int] * 3 + [_ptr, ctypes.c_longlong, _ptr, _c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _ptr, _c_int,
-                           _ptr, ctypes.c_longlong, _ptr, _ptr, _c_float, _ptr, ctypes.c_longlong, _ptr],
-    "demf_msda_fwd_raw_f32": [_c_int] * 7 + [_ptr, ctypes.c_longlong, _ptr, _ptr, _ptr, ctypes.c_longlong, _c_int, _c_int,
-                              _ptr, _ptr, _ptr],
-    "demf_msda_fwd_raw_head_f32": [_c_int] * 4 + [_ptr, ctypes.c_longlong, _ptr, _ptr, _ptr, ctypes.c_longlong, _c_int, _c_int,
-                                   _ptr, _ptr, _c_int, _c_int, _ptr],
-    "demf_invert_index": [_c_int] * 3 + [_ptr] * 4,
-    "demf_invert_index_ws": [_c_int] * 3 + [_ptr] * 5,
-    "demf_mlp_gemm_bwd_dw_group": [_c_int, _ptr, _ptr],
-    "demf_sa_index_chain": [_c_int] * 3 + [_ptr] * 4,
-    "demf_split_points": [ctypes.c_longlong, _c_int] + [_ptr] * 4,
-    "demf_group_concat_cl_bwd_gather": [_c_int] * 6 + [_ptr] * 5,
-    "demf_group_first_fwd": [_c_int] * 5 + [_c_float, _c_int] + [_ptr] * 5 + [_c_int] + [_ptr] * 4 + [_c_float] * 2 + [_ptr] * 6 + [_ptr],
-    "demf_group_first_bwd": [_c_int] * 5 + [_c_float, _c_int] + [_ptr] * 10 + [_c_int, _ptr, _c_int] + [_ptr] * 4,
-    "demf_adamw_f32": [ctypes.c_longlong] + [_ptr] * 5 + [_c_float] * 7 + [_c_int, _ptr],
-    "demf_multi_copy_sumsq": [_c_int, _ptr, _c_int, _ptr, _ptr],
-    "demf_sumsq_f32": [ctypes.c_longlong, _ptr, _ptr, _ptr],
-    "demf_adamw_state_f32": [_c_int] + [_ptr] * 9 + [_c_float] * 5 + [_ptr],
-    "demf_step_meter": [_c_int, _ptr, _ptr, _c_float, _c_float, _ptr, _c_int, _ptr],
-    "demf_multi_add": [_c_int, _ptr, _c_int, _ptr],
-    "demf_multi_add_sumsq": [_c_int, _ptr, _c_int, _ptr, _ptr],
-    "demf_scalars_accum": [_c_int, _ptr, _ptr, _c_float, _ptr],
-    "demf_store_concat": [_c_int, _ptr, _c_int, _c_int] + [_ptr] * 5 + [_c_int] * 2 + [_ptr] * 5 + [_ptr],
-    "demf_meter_merge": [_c_int, _c_int, _ptr, _ptr, _ptr],
-    "demf_mlp_gemm_fwd": [_c_int] * 4 + [_ptr] * 6,
-    "demf_mlp_gemm_fwd_pool": [_c_int] * 4 + [_ptr] * 5 + [_c_int] + [_ptr] * 5,
-    "demf_mlp_gemm_fwd_bn": [_c_int] * 4 + [_ptr] * 7 + [_c_float, _c_float] + [_ptr] * 7,
-    "demf_mlp_gemm_fwd_pool_bn": [_c_int] * 4 + [_ptr] * 5 + [_c_int] + [_ptr] * 6 + [_c_float, _c_float] + [_ptr] * 7,
-    "demf_mlp_gemm_fwd_bn_st": [_c_int] * 4 + [_ptr] * 7 + [_c_float, _c_float] + [_ptr] * 6 + [_c_int, _ptr],
-    "demf_mlp_gemm_fwd_pool_bn_st": [_c_int] * 4 + [_ptr] * 5 + [_c_int] + [_ptr] * 4 + [_c_float, _c_float] + [_ptr] * 6 + [_c_int, _ptr],
-    "demf_pool_select": [_c_int] * 2 + [_ptr] * 9,
-    "demf_pool_select_slot0": [_c_int] * 2 + [_ptr] * 7,
-    "demf_mlp_first_stats": [_c_int] * 2 + [_ptr] * 5 + [_c_float, _c_float] + [_ptr] * 7,
-    "demf_mlp_gemm_fwd_bn_x4": [_c_int] * 2 + [_ptr] * 8 + [_c_float, _c_float] + [_ptr] * 7,
-    "demf_mlp_bwd_fused_x4": [_c_int] * 3 + [_ptr] * 11,
-    "demf_mlp_bwd_pool": [_c_int] * 4 + [_ptr] * 17,
-    "demf_mlp_bwd_pool_ws": [_c_int, _ptr],
-    "demf_bn_finalize": [_c_int, ctypes.c_longlong] + [_ptr] * 3 + [_c_float, _c_float] + [_ptr] * 7,
-    "demf_l2norm_rows_fwd": [_c_int] * 2 + [_ptr] * 4,
-    "demf_l2norm_rows_bwd": [_c_int] * 2 + [_ptr] * 5,
-    "demf_vote_combine_fwd": [_c_int] * 2 + [_ptr] * 7,
-    "demf_vote_combine_bwd": [_c_int] * 2 + [_ptr] * 7,
-    "demf_bnrelu_maxpool_fwd": [_c_int] * 3 + [_ptr] * 5,
-    "demf_bn_bwd_reduce": [_c_int] * 3 + [_ptr] * 9,
-    "demf_bn_bwd_vectors": [_c_int, ctypes.c_longlong] + [_ptr] * 8,
-    "demf_mlp_gemm_bwd_dx": [_c_int] * 4 + [_ptr] * 3 + [_c_int] + [_ptr] * 5,
-    "demf_mlp_gemm_bwd_dx_first": [_c_int] * 3 + [_ptr] * 10,
-    "demf_mlp_first_finish": [_c_int, ctypes.c_longlong] + [_ptr] * 7,
-    "demf_mlp_gemm_bwd_dx_red": [_c_int] * 4 + [_ptr] * 3 + [_c_int] + [_ptr] * 9,
-    "demf_mlp_gemm_bwd_dx_w": [_c_int] * 4 + [_ptr] * 3 + [_c_int] + [_ptr] * 5,
-    "demf_mlp_bwd_fused": [_c_int] * 3 + [_ptr] * 3 + [_c_int] + [_ptr] * 15 + [_c_int, _ptr],
-    "demf_mlp_bwd_fused_cols": [_c_int] * 5 + [_ptr] * 3 + [_c_int] + [_ptr] * 14,
-    "demf_mlp_bwd_fused_wide": [_c_int] * 3 + [_ptr] * 3 + [_c_int] + [_ptr] * 14,
-    "demf_mlp_last_form": [],
-    "demf_switch_at": [_c_int, _ptr, _ptr, _ptr],
-    "demf_mlp_gemm_bwd_dx_red_v": [_c_int] * 4 + [_ptr] * 3 + [_c_int] + [_ptr] * 13,
-    "demf_bn_bwd_reduce_vectors": [_c_int] * 3 + [_ptr] * 11 + [_c_int, _ptr],
-    "demf_mlp_gemm_bwd_dw": [_c_int] * 4 + [_ptr] * 3 + [_c_int] + [_ptr] * 6,
-    "demf_mlp_gemm_bwd_dw_ld": [_c_int] * 4 + [_ptr] * 3 + [_c_int] + [_ptr] * 5 + [_c_int, _ptr],
-    "demf_head_loss_fwd": [_c_int] * 3 + [_ptr] * 14,
-    "demf_head_loss_bwd": [_c_int] * 3 + [_ptr] * 17,
-    "demf_ca_head_loss_fwd": [_c_int] * 3 + [_ptr] * 12,
-    "demf_ca_head_loss_bwd": [_c_int] * 3 + [_ptr] * 16,
-    "demf_vote_loss": [_c_int] * 4 + [_c_float] + [_ptr] * 10,
-    "demf_vote_loss_fwd": [_c_int] * 4 + [_c_float] + [_ptr] * 8,
-    "demf_msda_fwd_f32": [_c_int] * 7 + [_ptr] * 7,
-    "demf_msda_bwd_f32": [_c_int] * 7 + [_ptr] * 10,
-    "demf_msda_fwd_bf16": [_c_int] * 7 + [_ptr] * 7,
-    "demf_msda_bwd_bf16": [_c_int] * 7 + [_ptr] * 10,
-    "demf_gemm_f32": [_ptr, _ptr],
-    "demf_gemm_group_f32": [_ptr, _c_int, _ptr],
-    "demf_set_compute_dtype": [_c_int],
-    "demf_set_f16_terms": [_c_int],
-    "demf_get_compute_dtype": [],
-    "demf_ctx_push": [_ptr],
-    "demf_ctx_pop": [],
-    "demf_gemm_f32_ctx": [_ptr] * 3,
-    "demf_gemm_group_f32_ctx": [_ptr, _ptr, _c_int, _ptr],
-    "demf_mlp_gemm_fwd_ctx": [_ptr] + [_c_int] * 4 + [_ptr] * 6,
-    "demf_multi_copy": [_c_int, _ptr, _c_int, _ptr],
-    "demf_zero_f32": [ctypes.c_longlong, _ptr, _ptr],
-    "demf_add_dropout_ln_fwd": [_c_int] * 2 + [_ptr] * 4 + [_c_float] * 2 + [_ptr, _c_int] + [_ptr] * 4,
-    "demf_add_dropout_ln_bwd": [_c_int] * 2 + [_ptr] * 5 + [_c_float, _ptr, _c_int, _ptr, _c_int] + [_ptr] * 4,
-    "demf_attn_core_fwd": [_c_int] * 4 + [_ptr, _c_float, _c_float, _ptr, _c_int] + [_ptr] * 5,
-    "demf_attn_core_bwd": [_c_int] * 4 + [_ptr] * 4 + [_c_float, _c_float, _ptr, _c_int] + [_ptr] * 2,
-    "demf_softmax_dropout_fwd": [_c_int] * 2 + [_ptr, _c_float, _ptr, _c_int] + [_ptr] * 3,
-    "demf_softmax_dropout_bwd": [_c_int] * 2 + [_ptr, _c_float, _ptr, _c_int] + [_ptr] * 2,
-    "demf_msda_prep_fwd": [_c_int] * 5 + [_ptr] * 10,
-    "demf_msda_prep_bwd": [_c_int] * 5 + [_ptr] * 14,
-    "demf_rng_advance": [_ptr, _ptr],
-    "demf_rng_next": [_ptr, _ptr, _ptr],
-    "demf_dropout_mask": [ctypes.c_longlong, _c_float, _ptr, _c_int, _ptr, _ptr],
-}
+_BY_VALUE = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double,
+             "long long": ctypes.c_longlong, "unsigned": ctypes.c_uint, "demf_stream_t": ctypes.c_void_p}
+_DECLARATOR = re.compile(r"(.*?)\b(\w+)\s*(?:\[\s*(\d+)\s*\])?", re.S)
 
 
-class DwJob(ctypes.Structure):
-    """include/demf_hip.h: demf_dw_job (field order and types must match)."""
-    _fields_ = [("R", _c_int), ("N", _c_int), ("K", _c_int), ("ldx", _c_int), ("G", _ptr), ("dP", _ptr), ("arg", _ptr),
-                ("ns", _c_int), ("Y", _ptr), ("vec6", _ptr), ("Xprev", _ptr), ("prev_scale_shift", _ptr), ("dW", _ptr),
-                ("lddw", _c_int)]
+def _declarator(text, where, base=None):
+    """'const float* x' / 'long long n' / 'int reserved[7]' -> (name, the base type's text, ctypes class).  Pointers
+    are c_void_p; ``base``: the type of a further declarator of 'int M, N, K'."""
+    m = _DECLARATOR.fullmatch(text.strip())
+    if m is None:
+        raise ValueError(f"{where}: cannot read the declaration {text.strip()!r}")
+    ctype, name, dim = m.groups()
+    ctype = base if base is not None and not ctype.strip() else ctype
+    key = " ".join(t for t in ctype.split() if t != "const")
+    if "*" in key:
+        cls = ctypes.c_void_p
+    elif key in _BY_VALUE:
+        cls = _BY_VALUE[key]
+    else:
+        raise ValueError(f"{where}: unknown by-value type {key!r} in {text.strip()!r}")
+    return name, ctype, cls * int(dim) if dim else cls
 
 
-class DetectLayer(ctypes.Structure):
-    """include/demf_hip.h: demf_detect_layer (field order and types must match)."""
-    _fields_ = [("K", _c_int), ("res_scale", _c_float)] + [
-        f for name in ("center", "center_base", "size", "dir_class", "dir_res", "obj", "sem")
-        for f in ((name, _ptr), ((name if name != "center_base" else "base") + "_sb", _c_int),
-                  ((name if name != "center_base" else "base") + "_sk", _c_int))]
+def _struct(name, body):
+    fields = []
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        base = None
+        for part in decl.split(","):
+            field, base, cls = _declarator(part, f"struct {name}", base)
+            fields.append((field, cls))
+    return type(name, (ctypes.Structure,), {"_fields_": fields, "__doc__": f"include/demf_hip.h: {name}"})
 
 
-class GemmDesc(ctypes.Structure):
-    """include/demf_hip.h: demf_gemm_desc (field order and types must match)."""
-    _ll = ctypes.c_longlong
-    _fields_ = [
-        ("M", _c_int), ("N", _c_int), ("K", _c_int), ("batch", _c_int), ("zdiv", _c_int),
-        ("splitk", _c_int),
-        ("A", _ptr), ("sam", _ll), ("sak", _ll), ("sab", _ll), ("sab2", _ll),
-        ("A2", _ptr), ("a2_cols", _c_int),
-        ("B", _ptr), ("sbn", _ll), ("sbk", _ll), ("sbb", _ll), ("sbb2", _ll),
-        ("B2", _ptr), ("b2_rows", _c_int),
-        ("C", _ptr), ("scm", _ll), ("scb", _ll), ("scb2", _ll),
-        ("C2", _ptr),
-        ("bias", _ptr), ("sbias_b", _ll),
-        ("rowscale", _ptr), ("srs_m", _ll), ("srs_b", _ll),
-        ("alpha", _c_float),
-        ("flags", _c_int),
-        ("gate", _ptr), ("sgm", _ll), ("sgb", _ll),
-        ("gate_scale", _c_float),
-        ("drop_p", _c_float),
-        ("rng", _ptr),
-        ("op_id", _c_int),
-        ("asum", _ptr),
-    ]
+def _int_expr(text, where):
+    """Value of '3', '(-1)' or '(1u << 16)': an integer, optionally shifted, optionally in parentheses."""
+    m = re.fullmatch(r"(\()?\s*(-?\d+|0[xX][0-9a-fA-F]+)[uUlL]*\s*(?:<<\s*(\d+)\s*)?(?(1)\))", text)
+    if m is None:
+        raise ValueError(f"{where}: cannot evaluate {text!r}")
+    return int(m.group(2), 0) << int(m.group(3) or 0)
+
+
+def parse_header(text):
+    """-> (prototypes: name -> (restype, [argtypes]), structs: name -> ctypes.Structure class, constants: name -> int)
+    of a header in the style of include/demf_hip.h."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {}
+    for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+)(.*)$", text, flags=re.M):
+        if m.group(2).strip():                      # (a bare name is a marker: the include guard, DEMF_INTERNAL)
+            constants[m.group(1)] = _int_expr(m.group(2).strip(), "#define " + m.group(1))
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    text = re.sub(r'\bDEMF_INTERNAL\b|extern\s+"C"\s*\{', " ", text)
+    struct = re.compile(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;")
+    structs = {m.group(1): _struct(m.group(1), m.group(2)) for m in struct.finditer(text)}
+    *decls, tail = struct.sub("", text).split(";")
+    protos = {}
+    for decl in decls:
+        decl = " ".join(decl.split())
+        f = re.fullmatch(r"(int|const char ?\*) ?(demf_\w+) ?\(([^(){}]*)\)", decl)
+        if f:
+            args = f.group(3).strip()
+            protos[f.group(2)] = (ctypes.c_int if f.group(1) == "int" else ctypes.c_char_p,
+                                  [] if args in ("", "void") else
+                                  [ctypes.c_void_p if "*" in a or "[" in a else _declarator(a, f.group(2))[2]
+                                   for a in args.split(",")])
+        elif decl != "typedef void* demf_stream_t":
+            raise ValueError(f"unknown declaration: {decl!r}")
+    if tail.strip() not in ("", "}"):                   # (the brace that closes extern "C")
+        raise ValueError(f"unknown declaration: {tail.strip()!r}")
+    return protos, structs, constants
+
+
+with open(HEADER_PATH) as _f:
+    _PROTOS, STRUCTS, CONSTANTS = parse_header(_f.read())
+# name -> argtypes of every entry point that returns a status (demf_version / demf_last_error: see load())
+SIGNATURES = {n: a for n, (_, a) in _PROTOS.items() if n not in ("demf_version", "demf_last_error")}
+DwJob, DetectLayer, GemmDesc, Ctx, OptState = (STRUCTS["demf_" + n] for n in
+                                               ("dw_job", "detect_layer", "gemm_desc", "ctx", "opt_state"))
 
 _lib = None
 
@@ -227,13 +111,9 @@ def load():
     # device is detected" at the first launch - seen with build() and smoke() in one process)
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    lib.demf_version.restype = _c_int
-    lib.demf_version.argtypes = []
-    lib.demf_last_error.restype = ctypes.c_char_p
-    lib.demf_last_error.argtypes = []
-    for name, argtypes in SIGNATURES.items():
+    for name, (restype, argtypes) in _PROTOS.items():
         fn = getattr(lib, name)  # AttributeError if the ABI drifted
-        fn.restype = _c_int
+        fn.restype = restype
         fn.argtypes = argtypes
     _lib = lib
     return lib

@@ -12,14 +12,6 @@
 
 namespace demf {
 
-// the head of csrc/optim.hip's OptState (layout documented in include/demf_hip.h)
-struct AccumOptState {
-  double sumsq;
-  long long t;
-  unsigned ticket;
-  float lr_factor;
-};
-
 // n segments, dst += src, in ONE launch: blockIdx.y = segment, blockIdx.x strides over its fp32 words.
 // table (device, 3 x n int64): src | dst | words, as multi_copy_k's.  A null source adds nothing: dst is not written.
 __global__ __launch_bounds__(256) void multi_add_k(int n, const long long* __restrict__ table) {
@@ -52,7 +44,7 @@ __global__ __launch_bounds__(256) void multi_add_k(int n, const long long* __res
 // partial is 0).  A null-source segment is read and its squares counted: the norm is that of the whole accumulated
 // buffer, not of this pass's share.
 __global__ __launch_bounds__(256) void multi_add_sumsq_k(int n, const long long* __restrict__ table,
-                                                         AccumOptState* st) {
+                                                         demf_opt_state* st) {
   __shared__ double part[4];
   const int seg = blockIdx.y;
   const float* src = reinterpret_cast<const float*>(table[seg]);
@@ -142,7 +134,7 @@ extern "C" int demf_multi_add_sumsq(int n, const void* table, int blocks_per_seg
   if (n == 0) return DEMF_OK;
   DEMF_REQUIRE(table != nullptr && opt_state != nullptr, "multi_add_sumsq: null pointer");
   hipLaunchKernelGGL(multi_add_sumsq_k, dim3(blocks_per_segment, n), dim3(256), 0, (hipStream_t)stream, n,
-                     (const long long*)table, (AccumOptState*)opt_state);
+                     (const long long*)table, (demf_opt_state*)opt_state);
   return check_launch("multi_add_sumsq");
 }
 

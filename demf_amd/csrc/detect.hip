@@ -8,10 +8,8 @@
 
 namespace demf {
 
-constexpr int DETECT_MAX_LAYERS = 8;
-
 struct DetectLayers {
-  demf_detect_layer l[DETECT_MAX_LAYERS];
+  demf_detect_layer l[DEMF_DETECT_MAX_LAYERS];
 };
 
 __device__ __forceinline__ const float* row_of(const float* p, int sb, int sk, int b, int k) {
@@ -100,7 +98,7 @@ __global__ __launch_bounds__(256) void detect_decode_k(int B, int K, int L, int 
   const int b = g / K, kk = g - b * K;
   int lo = 0;
 #pragma unroll
-  for (int i = 0; i < DETECT_MAX_LAYERS; ++i) {
+  for (int i = 0; i < DEMF_DETECT_MAX_LAYERS; ++i) {
     if (i < L) {
       const int Kl = layers.l[i].K;
       if (kk >= lo && kk < lo + Kl)
@@ -223,7 +221,7 @@ extern "C" int demf_detect_decode(int B, int K, int L, int C, int num_dir_bins, 
                                   const demf_detect_layer* layers, float* box7, float* cos_yaw,
                                   float* sin_yaw, float* obj, float* sem, int64_t* classes,
                                   demf_stream_t stream) {
-  DEMF_REQUIRE(B >= 0 && K >= 0 && L >= 1 && L <= DETECT_MAX_LAYERS && C >= 1 && num_dir_bins >= 1,
+  DEMF_REQUIRE(B >= 0 && K >= 0 && L >= 1 && L <= DEMF_DETECT_MAX_LAYERS && C >= 1 && num_dir_bins >= 1,
                "detect_decode: bad sizes");
   DEMF_REQUIRE(layers, "detect_decode: null pointer");
   long long sum = 0;

@@ -13,8 +13,8 @@ namespace demf {
 namespace {
 
 constexpr int kMatchThreads = 256;
-constexpr int kMatchMaxGt = 256;     // ground-truth boxes of one (class, scene) segment
-constexpr int kMatchMaxPred = 4096;  // detections of one (class, scene) segment
+constexpr int kMatchMaxGt = DEMF_EVAL_MAX_GT_PER_SEGMENT;      // ground-truth boxes of one (class, scene) segment
+constexpr int kMatchMaxPred = DEMF_EVAL_MAX_PRED_PER_SEGMENT;  // detections of one (class, scene) segment
 constexpr int kApThreads = 512;
 constexpr int kApPerThread = 16;     // consecutive detections per thread and chunk
 constexpr int kMaxThr = 4;

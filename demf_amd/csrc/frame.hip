@@ -23,7 +23,8 @@ namespace {
 constexpr int kFrameThreads = 256;
 constexpr int kFrameWaves = kFrameThreads / 64;
 constexpr int kFrameRounds = 4;
-constexpr int kFrameTile = kFrameThreads * kFrameRounds;      // ops.FRAME_TILE
+constexpr int kFrameTile = kFrameThreads * kFrameRounds;
+static_assert(kFrameTile == DEMF_FRAME_TILE, "the tile of include/demf_hip.h, by which callers size tile_counts");
 
 struct FrameArgs {
   int B, shift;

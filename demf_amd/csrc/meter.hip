@@ -11,18 +11,10 @@
 
 namespace demf {
 
-// the head of csrc/optim.hip's OptState as the meter reads it (layout documented in include/demf_hip.h)
-struct MeterOptState {
-  double sumsq;
-  long long t;
-  unsigned ticket;
-  float lr_factor;
-};
-
 struct MeterArgs {
   const float* s[DEMF_METER_MAX_SCALARS];
   int n;
-  const MeterOptState* st;
+  const demf_opt_state* st;
   float grad_scale, max_norm;
   unsigned* ring;
   int rows;
@@ -84,7 +76,7 @@ extern "C" int demf_step_meter(int n, const float* const* scalars, const void* o
     a.s[i] = i < n ? scalars[i] : nullptr;
   }
   a.n = n;
-  a.st = (const MeterOptState*)opt_state;
+  a.st = (const demf_opt_state*)opt_state;
   a.grad_scale = grad_scale;
   a.max_norm = max_norm;
   a.ring = (unsigned*)ring;

@@ -90,19 +90,14 @@ __global__ __launch_bounds__(256) void multi_copy_k(int n, const long long* __re
 // ---- optimizer step with DEVICE-resident state -------------------------------------------------
 // The step count, the learning-rate factor and the squared gradient norm live on the device, so the
 // whole update (norm + clip + AdamW) is capturable in the step's hipGraph: no host argument changes
-// between replays.  64 bytes:
+// between replays.  demf_opt_state (include/demf_hip.h):
 //   double sumsq        accumulated by multi_copy_sumsq_k / sumsq_k, cleared by the AdamW launch
 //   long long t         completed optimizer steps
 //   unsigned ticket     last-workgroup detection of the AdamW launch (atomics only, no fence)
 //   float lr_factor     multiplies every group's base learning rate (step schedule)
-struct OptState {
-  double sumsq;
-  long long t;
-  unsigned ticket;
-  float lr_factor;
-};
+static_assert(sizeof(demf_opt_state) == 64, "the optimizer's device state block is 64 bytes");
 
-__device__ __forceinline__ void block_add_sumsq(float acc, OptState* st) {
+__device__ __forceinline__ void block_add_sumsq(float acc, demf_opt_state* st) {
   __shared__ double part[4];
   double d = (double)acc;
   for (int off = 32; off; off >>= 1) d += __shfl_xor(d, off);
@@ -119,7 +114,7 @@ __device__ __forceinline__ void block_add_sumsq(float acc, OptState* st) {
 // multi_copy_k + the sum of squares of everything copied (fp32 words), added to st->sumsq: the
 // gradient pack of the captured step takes the clip norm on the way.
 __global__ __launch_bounds__(256) void multi_copy_sumsq_k(int n, const long long* __restrict__ table,
-                                                          OptState* st) {
+                                                          demf_opt_state* st) {
   const int seg = blockIdx.y;
   const float* src = reinterpret_cast<const float*>(table[seg]);
   float* dst = reinterpret_cast<float*>(table[n + seg]);
@@ -154,7 +149,7 @@ __global__ __launch_bounds__(256) void multi_copy_sumsq_k(int n, const long long
   block_add_sumsq(acc, st);
 }
 
-__global__ __launch_bounds__(256) void sumsq_k(long long n, const float* __restrict__ x, OptState* st) {
+__global__ __launch_bounds__(256) void sumsq_k(long long n, const float* __restrict__ x, demf_opt_state* st) {
   const long long stride = (long long)gridDim.x * blockDim.x;
   float acc = 0.f;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) acc += x[i] * x[i];
@@ -185,7 +180,7 @@ struct AdamWStateArgs {
   const float* g;
   float* m;
   float* v;
-  OptState* st;
+  demf_opt_state* st;
   float max_norm, grad_scale, beta1, beta2, eps;
 };
 
@@ -197,7 +192,7 @@ __device__ unsigned g_adamw_tickets[TK_GROUPS * TK_PITCH];
 // workgroup to finish (ticket) publishes t, clears sumsq and the ticket for the next step.
 __global__ __launch_bounds__(256) void adamw_state_k(AdamWStateArgs a) {
   __shared__ float sh[4];
-  OptState* st = a.st;
+  demf_opt_state* st = a.st;
   int s = 0;
   for (int k = 1; k < a.nseg; ++k)
     if (blockIdx.x >= a.seg[k].block0) s = k;
@@ -344,7 +339,7 @@ extern "C" int demf_multi_copy_sumsq(int n, const void* table, int blocks_per_se
   if (n == 0) return DEMF_OK;
   DEMF_REQUIRE(table != nullptr && opt_state != nullptr, "multi_copy_sumsq: null pointer");
   hipLaunchKernelGGL(multi_copy_sumsq_k, dim3(blocks_per_segment, n), dim3(256), 0, (hipStream_t)stream, n,
-                     (const long long*)table, (OptState*)opt_state);
+                     (const long long*)table, (demf_opt_state*)opt_state);
   return check_launch("multi_copy_sumsq");
 }
 
@@ -354,7 +349,7 @@ extern "C" int demf_sumsq_f32(long long n, const float* x, void* opt_state, demf
   long long blocks = (n + 2047) / 2048;
   if (blocks > 1024) blocks = 1024;
   hipLaunchKernelGGL(sumsq_k, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n, x,
-                     (OptState*)opt_state);
+                     (demf_opt_state*)opt_state);
   return check_launch("sumsq");
 }
 
@@ -380,7 +375,7 @@ extern "C" int demf_adamw_state_f32(int nseg, const long long* seg_start, const 
     if (b > 1024) b = 1024;
     blocks += (unsigned)b;
   }
-  a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.st = (OptState*)opt_state;
+  a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.st = (demf_opt_state*)opt_state;
   a.max_norm = max_norm; a.grad_scale = grad_scale; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
   hipLaunchKernelGGL(adamw_state_k, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("adamw_state");

@@ -16,14 +16,14 @@
 
 namespace demf {
 
-constexpr int RANKS_MAX = 64;        // W of either merge (the per-rank tables travel in the kernel arguments)
+// DEMF_RANKS_MAX bounds W of either merge: the per-rank tables travel in the kernel arguments
 constexpr int CONCAT_THREADS = 256;
 constexpr int CONCAT_MAX_BLOCKS = 1024;   // workgroups per rank; a workgroup strides over its rank's words
 
 struct ConcatArgs {
-  int n[RANKS_MAX];        // scenes of rank r
-  int first[RANKS_MAX];    // scenes of the ranks before r
-  int W, S, R;             // ranks, per-rank scene capacity, per-rank row capacity
+  int n[DEMF_RANKS_MAX];      // scenes of rank r
+  int first[DEMF_RANKS_MAX];  // scenes of the ranks before r
+  int W, S, R;                // ranks, per-rank scene capacity, per-rank row capacity
   int total_scenes;
   const int* src_off;      // (W, S+1)
   const int* src_state;    // (W, 2)
@@ -41,11 +41,11 @@ struct ConcatArgs {
 // grid (P, W), 256 threads.  Every workgroup reads the W row counts (lane q of the first wave: scene_off[q][n_q]),
 // takes the exclusive prefix for its own rank from LDS and copies a strided share of the rank's words.
 __global__ __launch_bounds__(CONCAT_THREADS) void store_concat_k(ConcatArgs a) {
-  __shared__ int rows_s[RANKS_MAX];
-  __shared__ int flag_s[RANKS_MAX];
+  __shared__ int rows_s[DEMF_RANKS_MAX];
+  __shared__ int flag_s[DEMF_RANKS_MAX];
   const int tid = threadIdx.x;
   const int r = blockIdx.y;
-  if (tid < RANKS_MAX) {
+  if (tid < DEMF_RANKS_MAX) {
     int rows = 0, flag = 0;
     if (tid < a.W) {
       rows = a.src_off[(size_t)tid * (a.S + 1) + a.n[tid]];
@@ -139,8 +139,8 @@ extern "C" int demf_store_concat(int W, const int* counts, int S, int R, const i
                                  int* labels, int* scene_off, int* state, demf_stream_t stream) {
   DEMF_REQUIRE(W >= 1 && S >= 1 && R >= 0 && max_scenes >= 1 && max_rows >= 0,
                "store_concat: bad sizes (W=%d S=%d R=%d max_scenes=%d max_rows=%d)", W, S, R, max_scenes, max_rows);
-  if (W > RANKS_MAX) {
-    set_error("store_concat: W=%d ranks (at most %d supported)", W, RANKS_MAX);
+  if (W > DEMF_RANKS_MAX) {
+    set_error("store_concat: W=%d ranks (at most %d supported)", W, DEMF_RANKS_MAX);
     return DEMF_EUNSUPPORTED;
   }
   DEMF_REQUIRE(counts != nullptr && src_scene_off != nullptr && src_state != nullptr && scene_off != nullptr &&
@@ -154,7 +154,7 @@ extern "C" int demf_store_concat(int W, const int* counts, int S, int R, const i
                "store_concat: too many rows for the offsets (R=%d max_rows=%d)", R, max_rows);
   ConcatArgs a;
   long long scenes = 0;
-  for (int r = 0; r < RANKS_MAX; ++r) {
+  for (int r = 0; r < DEMF_RANKS_MAX; ++r) {
     const int n = r < W ? counts[r] : 0;
     DEMF_REQUIRE(n >= 0 && n <= S, "store_concat: rank %d holds %d scenes, its capacity is %d", r, n, S);
     a.n[r] = n;
@@ -188,8 +188,8 @@ extern "C" int demf_store_concat(int W, const int* counts, int S, int R, const i
 
 extern "C" int demf_meter_merge(int W, int rows, const void* rings, void* out, demf_stream_t stream) {
   DEMF_REQUIRE(W >= 1 && rows >= 1, "meter_merge: bad sizes (W=%d rows=%d)", W, rows);
-  if (W > RANKS_MAX) {
-    set_error("meter_merge: W=%d ranks (at most %d supported)", W, RANKS_MAX);
+  if (W > DEMF_RANKS_MAX) {
+    set_error("meter_merge: W=%d ranks (at most %d supported)", W, DEMF_RANKS_MAX);
     return DEMF_EUNSUPPORTED;
   }
   DEMF_REQUIRE(rings != nullptr && out != nullptr, "meter_merge: null pointer");

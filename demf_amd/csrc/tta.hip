@@ -13,8 +13,8 @@ namespace demf {
 
 namespace {
 
-constexpr int kNmsMax = 1024;          // boxes of one NMS segment (one lane each)
-constexpr int kMergeMaxCand = 16384;   // candidates of one merged scene (V * K * C): 128 KB of sort LDS
+constexpr int kNmsMax = DEMF_NMS_MAX_SEGMENT;           // boxes of one NMS segment (one lane each)
+constexpr int kMergeMaxCand = DEMF_TTA_MAX_CANDIDATES;  // candidates of one merged scene (V * K * C): 128 KB of sort LDS
 constexpr int kGatherThreads = 256;
 constexpr int kFinishThreads = 1024;
 

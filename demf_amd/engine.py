@@ -232,6 +232,7 @@ class FlatAdamW:
 
     def __init__(self, groups, flat_grads, betas=(0.9, 0.999), eps=1e-8):
         import ctypes
+        from ._ffi import OptState
         params = flat_grads.params
         assert [id(p) for g in groups for p in g["params"] if p.requires_grad] == [id(p) for p in params]
         self.grads = flat_grads.flat
@@ -259,19 +260,19 @@ class FlatAdamW:
         self.exp_avg = torch.zeros_like(self.flat)
         self.exp_avg_sq = torch.zeros_like(self.flat)
         self.betas, self.eps = betas, eps
-        # { double sumsq; int64 t; uint32 ticket; float lr_factor; pad } - include/demf_hip.h
-        self.state = torch.zeros(64, dtype=torch.uint8, device=self.flat.device)
+        self.state = torch.zeros(ctypes.sizeof(OptState), dtype=torch.uint8, device=self.flat.device)
+        self._t_word, self._lr_word = OptState.t.offset // 8, OptState.lr_factor.offset // 4    # of int64 / fp32 views
         self._lr_factor = 1.0
-        self.state.view(torch.float32)[5] = 1.0
+        self.state.view(torch.float32)[self._lr_word] = 1.0
 
     @property
     def t(self):
         """Completed optimizer steps (read from the device: synchronises)."""
-        return int(self.state.view(torch.int64)[1].item())
+        return int(self.state.view(torch.int64)[self._t_word].item())
 
     @t.setter
     def t(self, value):
-        self.state.view(torch.int64)[1] = int(value)
+        self.state.view(torch.int64)[self._t_word] = int(value)
 
     @property
     def lr_factor(self):
@@ -282,7 +283,7 @@ class FlatAdamW:
         lr_config step=[24, 32], x0.1 each - configs/_base_/schedules/schedule_3x.py:7-9).
         Written into the device state: captured steps pick it up at their next replay."""
         self._lr_factor = float(factor)
-        self.state.view(torch.float32)[5] = float(factor)
+        self.state.view(torch.float32)[self._lr_word] = float(factor)
 
     def check_aliasing(self):
         """Every parameter must still be a view of the flat buffer: ``model.to()`` / ``.float()`` /

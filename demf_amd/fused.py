@@ -34,7 +34,8 @@ from torch.autograd.function import once_differentiable
 
 from . import _ffi
 
-RELU, DROPOUT, GATE, ACCUM, ROWBIAS, ACCUM2 = 1, 2, 4, 8, 16, 32
+RELU, DROPOUT, GATE, ACCUM, ROWBIAS, ACCUM2 = (_ffi.CONSTANTS["DEMF_GEMM_" + n] for n in
+                                                ("RELU", "DROPOUT", "GATE", "ACCUM", "ROWBIAS", "ACCUM2"))
 
 # dropout streams of the layer
 OP_ATTN, OP_LN1, OP_LN2, OP_FFN, OP_LN3 = 1, 2, 3, 4, 5

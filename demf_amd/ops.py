@@ -2032,7 +2032,7 @@ def aligned_nms(extent, scores, classes, valid, iou_thr, as_bytes=False):
     return keep if as_bytes else keep.bool()
 
 
-DETECT_MAX_LAYERS = 8
+DETECT_MAX_LAYERS = _ffi.CONSTANTS["DEMF_DETECT_MAX_LAYERS"]
 _DETECT_FIELDS = (("center", "center", 3), ("center_base", "base", 3), ("size", "size", 3),
                   ("dir_class", "dir_class", None), ("dir_res", "dir_res", None), ("obj", "obj", 2),
                   ("sem", "sem", None))
@@ -2133,8 +2133,8 @@ def detect_pack(keep, obj, sem, classes, boxes_bottom, score_thr, per_class, fir
 # --------------------------------------------------------------------------
 # Test-time augmentation (csrc/tta.hip; tta.merge_views composes these)
 # --------------------------------------------------------------------------
-NMS_MAX_SEGMENT = 1024            # boxes of one NMS segment: V * K of a merge
-TTA_MAX_CANDIDATES = 16384        # V * K * C of a merged scene
+NMS_MAX_SEGMENT = _ffi.CONSTANTS["DEMF_NMS_MAX_SEGMENT"]              # boxes of one NMS segment: V * K of a merge
+TTA_MAX_CANDIDATES = _ffi.CONSTANTS["DEMF_TTA_MAX_CANDIDATES"]        # V * K * C of a merged scene
 NMS_MODES = {"bev": 0, "aligned": 1, "3d": 2}
 
 
@@ -2248,8 +2248,8 @@ def nms_normal_gpu(boxes, scores, thresh):
 # --------------------------------------------------------------------------
 # Indoor detection evaluation (csrc/eval3d.hip; evaluation.indoor_eval composes these)
 # --------------------------------------------------------------------------
-EVAL_MAX_PRED_PER_SEGMENT = 4096
-EVAL_MAX_GT_PER_SEGMENT = 256
+EVAL_MAX_PRED_PER_SEGMENT = _ffi.CONSTANTS["DEMF_EVAL_MAX_PRED_PER_SEGMENT"]
+EVAL_MAX_GT_PER_SEGMENT = _ffi.CONSTANTS["DEMF_EVAL_MAX_GT_PER_SEGMENT"]
 
 
 def box3d_overlaps(boxes1, boxes2):
@@ -2387,7 +2387,7 @@ def image_prep(src, offsets, shapes, pad_shape, mean=IMG_NORM[0], std=IMG_NORM[1
 # --------------------------------------------------------------------------
 # RGB-D frame front end (csrc/frame.hip): depth + colour + calibration -> the raw records of the input pipeline
 # --------------------------------------------------------------------------
-FRAME_TILE = 1024                 # pixels per workgroup: kFrameTile of csrc/frame.hip (the entry point checks it)
+FRAME_TILE = _ffi.CONSTANTS["DEMF_FRAME_TILE"]        # pixels per workgroup: kFrameTile of csrc/frame.hip
 
 
 def depth_to_points(depth, depth_off, rgb, rgb_off, shapes, calib, shift=3, out=None):
@@ -2577,8 +2577,8 @@ def msda_sample_then_project(tokens, keep4, spatial_shapes, level_start_index, s
 # --------------------------------------------------------------------------
 # Step meter (csrc/meter.hip)
 # --------------------------------------------------------------------------
-METER_ROW_WORDS, METER_HEAD_WORDS, METER_MAX_SCALARS = 16, 6, 10      # include/demf_hip.h: DEMF_METER_*
-METER_FLAG_GRAD_NORM = 1 << 16
+METER_ROW_WORDS, METER_HEAD_WORDS, METER_MAX_SCALARS, METER_FLAG_GRAD_NORM = (
+    _ffi.CONSTANTS["DEMF_METER_" + n] for n in ("ROW_WORDS", "HEAD_WORDS", "MAX_SCALARS", "FLAG_GRAD_NORM"))
 
 
 def step_meter(scalars, opt_state, grad_scale, max_norm, ring):
@@ -2620,7 +2620,7 @@ def scalars_accum(scalars, acc, scale):
 # --------------------------------------------------------------------------
 # Rank merges (csrc/ranks.hip; ranks.py puts the collective in front)
 # --------------------------------------------------------------------------
-RANKS_MAX = 64                    # W of store_concat / meter_merge
+RANKS_MAX = _ffi.CONSTANTS["DEMF_RANKS_MAX"]        # W of store_concat / meter_merge
 
 
 def store_concat(counts, scene_off, state, boxes, scores, labels, out_boxes, out_scores, out_labels, out_scene_off,

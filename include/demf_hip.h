@@ -854,7 +854,8 @@ typedef struct demf_detect_layer {
   const float* sem; int sem_sb, sem_sk;
 } demf_detect_layer;
 
-/* Decode + score of get_bboxes (class_agnostic_vote_head.py:714-733) for L <= 8 ensemble layers (HOST array)
+#define DEMF_DETECT_MAX_LAYERS 8
+/* Decode + score of get_bboxes (class_agnostic_vote_head.py:714-733) for L <= DEMF_DETECT_MAX_LAYERS ensemble layers (HOST array)
  * in one launch, in the concatenated (B, K = sum K_l) layout: box7 (B,K,7) = the coder's decode (gravity
  * centre, size, yaw in [0, 2pi)), cos_yaw / sin_yaw (B,K), obj (B,K) = softmax(obj_scores)[..., 1],
  * sem (B,K,C) = softmax(sem_scores), classes (B,K) = argmax(sem).  K > 1024 returns DEMF_EUNSUPPORTED.   */
@@ -903,7 +904,10 @@ DEMF_INTERNAL int demf_box3d_iou(int N, int M, const float* boxes1, const float*
  * gt_boxes rows gt_off[s] .. gt_off[s+1) in that scene's order.  thresholds: T <= 4 IoU thresholds in HOST
  * memory.  tp (P,T) bytes in the caller's row order: 1 iff the row's best GT (first maximum) has
  * IoU > threshold and no earlier detection of the segment took it.  max_pred / max_gt: the largest segment;
- * above 4096 detections or 256 GT the call returns DEMF_EUNSUPPORTED.                                    */
+ * above DEMF_EVAL_MAX_PRED_PER_SEGMENT detections or DEMF_EVAL_MAX_GT_PER_SEGMENT GT the call returns
+ * DEMF_EUNSUPPORTED.                                                                                      */
+#define DEMF_EVAL_MAX_PRED_PER_SEGMENT 4096
+#define DEMF_EVAL_MAX_GT_PER_SEGMENT 256
 DEMF_INTERNAL int demf_eval_match(int S, int T, const float* thresholds, int max_pred, int max_gt,
                     const float* pred_boxes, const int* order, const int* pred_off, const float* gt_boxes,
                     const int* gt_off, unsigned char* tp, demf_stream_t stream);
@@ -930,8 +934,9 @@ DEMF_INTERNAL int demf_eval_ap(int C, int T, const int* cls_off, const int* npos
  * whose score is neither NaN nor -inf, visited in score order (descending; ties: the lower row first); a visited
  * candidate that is still alive is kept and removes every alive candidate with !(iou <= thr), so NaN removes.
  * keep (R) bytes: 0 / 1 for the rows of every segment; rows outside every segment are not written.  n_max: the host's
- * bound on seg_count, at most 1024 (beyond: DEMF_EUNSUPPORTED, nothing launched).  A segment whose count exceeds
+ * bound on seg_count, at most DEMF_NMS_MAX_SEGMENT (beyond: DEMF_EUNSUPPORTED, nothing launched).  A segment whose count exceeds
  * n_max on the device, or whose rows leave [0, R), sets *overflow = 1 and none of its keep bytes is written.      */
+#define DEMF_NMS_MAX_SEGMENT 1024
 DEMF_INTERNAL int demf_nms_bev(int R, int S, int n_max, float thr, int mode, const float* boxes, const float* scores,
                  const int* seg_start, const int* seg_count, const unsigned char* valid, unsigned char* keep,
                  int* overflow, demf_stream_t stream);
@@ -946,8 +951,9 @@ DEMF_INTERNAL int demf_nms_bev(int R, int S, int n_max, float thr, int mode, con
  * protocol (cursor read at scene_off[first_scene]; scene_off[first_scene + b + 1] and state[0] written; state[1] = 1
  * when rows do not fit, when a segment holds more than V * K rows, or when view_state[1] (may be NULL) is set; rows at
  * or beyond max_rows are not written).  Workspace: ws_boxes (B*C*V*K, 7), ws_scores (B*C*V*K), ws_seg (2*B*C + 1)
- * ints, ws_keep (B*C*V*K) bytes.  Three launches whatever the sizes, no host sync.  V * K > 1024 or
- * V * K * C > 16384 returns DEMF_EUNSUPPORTED with nothing launched.                                              */
+ * ints, ws_keep (B*C*V*K) bytes.  Three launches whatever the sizes, no host sync.  V * K > DEMF_NMS_MAX_SEGMENT or
+ * V * K * C > DEMF_TTA_MAX_CANDIDATES returns DEMF_EUNSUPPORTED with nothing launched.                            */
+#define DEMF_TTA_MAX_CANDIDATES 16384
 DEMF_INTERNAL int demf_tta_merge(int B, int V, int C, int K, float thr, int mode, int max_num, const float* view_boxes,
                    const float* view_scores, const int* view_labels, const int* view_scene_off,
                    const int* view_state, int first_view_scene, int view_max_scenes, int view_max_rows,
@@ -1001,8 +1007,9 @@ DEMF_INTERNAL int demf_image_prep(int B, int Hp, int Wp, long long src_bytes, co
  * raw (total, 6) fp32 receives the records of the valid pixels only, frames in order and row-major inside a frame;
  * rows at or beyond offsets[B] are not written.  offsets (B+1) int64 (DEVICE): offsets[b+1] - offsets[b] = frame b's
  * valid pixels - the (raw, offsets) pair of demf_points_floor / demf_points_prep.  A frame whose table entries do
- * not lie inside the buffers has no valid pixel.  tile_counts: ntiles = ceil(total / 1024) ints of scratch.  Two
- * launches, no atomics: the result is bit-identical from run to run.                                              */
+ * not lie inside the buffers has no valid pixel.  tile_counts: ntiles = ceil(total / DEMF_FRAME_TILE) ints of
+ * scratch.  Two launches, no atomics: the result is bit-identical from run to run.                                */
+#define DEMF_FRAME_TILE 1024
 DEMF_INTERNAL int demf_depth_to_points(int B, long long total, long long rgb_bytes, int shift,
                          const unsigned short* depth, const int64_t* depth_off, const unsigned char* rgb,
                          const int64_t* rgb_off, const int* shapes, const double* calib, int ntiles,
@@ -1021,14 +1028,20 @@ DEMF_INTERNAL int demf_adamw_f32(long long n, float* param, const float* grad, f
                    float beta2, float eps, float weight_decay, int step, demf_stream_t stream);
 
 /* The same update with its state ON THE DEVICE, so that norm + clip + AdamW are nodes of the step's
- * hipGraph (nothing the host passes changes between replays).  `opt_state`: 64 zero-initialised bytes
- *   { double sumsq; int64 t; uint32 ticket; float lr_factor; ... }
+ * hipGraph (nothing the host passes changes between replays).  `opt_state`: one zero-initialised demf_opt_state.
  * sumsq = squared L2 norm of the gradients of ALL groups, accumulated by demf_multi_copy_sumsq (the
  * gradient pack of a captured step) or demf_sumsq_f32 and cleared by demf_adamw_state_f32; t = completed
  * steps (the launch uses t + 1 for the bias corrections and publishes it from its last workgroup);
  * lr_factor multiplies every group's learning rate (the reference's step schedule,
  * configs/_base_/schedules/schedule_3x.py:7-9).  Up to 4 parameter groups (segments [start, start + n) of
  * the flat buffers, HOST arrays) in ONE launch; max_norm <= 0: no clipping.                            */
+typedef struct demf_opt_state {
+  double sumsq;
+  long long t;
+  unsigned ticket;    /* last-workgroup detection of the AdamW launch */
+  float lr_factor;
+  int reserved[10];   /* to 64 bytes */
+} demf_opt_state;
 DEMF_INTERNAL int demf_multi_copy_sumsq(int n, const void* table, int blocks_per_segment, void* opt_state,
                           demf_stream_t stream);
 DEMF_INTERNAL int demf_sumsq_f32(long long n, const float* x, void* opt_state, demf_stream_t stream);
@@ -1082,8 +1095,9 @@ DEMF_INTERNAL int demf_scalars_accum(int n, const float* const* scalars, float* 
 
 /* ------------------------------------------------------------------ *
  * Rank merges (csrc/ranks.hip): the device state of W data-parallel ranks, ALREADY GATHERED into rank-major
- * device arrays, merged into one.  No communication in here; W > 64 returns DEMF_EUNSUPPORTED.
+ * device arrays, merged into one.  No communication in here; W > DEMF_RANKS_MAX returns DEMF_EUNSUPPORTED.
  * ------------------------------------------------------------------ */
+#define DEMF_RANKS_MAX 64
 
 /* W DetectionStores -> one, in rank order.  counts: HOST array of W ints, n_r = the scenes rank r appended
  * (0 <= n_r <= S, sum <= max_scenes).  Sources, DEVICE, the ranks' arrays stacked: src_scene_off (W, S+1),
