@@ -88,3 +88,64 @@ class DetectionStore:
             labels = torch.zeros((0,), dtype=torch.int64)
         return [dict(boxes_3d=DepthBoxes(boxes[a:b].clone()), scores_3d=scores[a:b].clone(),
                      labels_3d=labels[a:b].clone()) for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
+
+
+class Detection2DStore:
+    """Device-resident 2D detections of many images, fixed shape (``modules.Detr2D.predict_into``; csrc/detr2d.hip:
+    demf_detr2d_select writes one image's block per workgroup, without a host sync):
+
+      rows (S,k,6) fp32 = [x1, y1, x2, y2, score, class] in the order (logit descending, flat index ascending),
+          zeros behind an image's ``counts`` rows;  counts (S,) int32;  flag (1,) int32, bit 0 = a NaN logit was met
+
+    ``score_thr``: the filter of ``extract_bboxes_2d`` (0.09 upstream); negative keeps all k places."""
+
+    def __init__(self, max_images, k=100, score_thr=0.09, device=None):
+        if int(max_images) < 1 or int(k) < 1:
+            raise ValueError(f"max_images and k must be positive, got {max_images} and {k}")
+        self.max_images, self.k, self.score_thr = int(max_images), int(k), float(score_thr)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.rows = torch.zeros((self.max_images, self.k, 6), dtype=torch.float32, device=self.device)
+        self.counts = torch.zeros((self.max_images,), dtype=torch.int32, device=self.device)
+        self.flag = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self._images = 0
+
+    def __len__(self):
+        return self._images
+
+    def reset(self):
+        """Forget every image (the arrays stay allocated)."""
+        self.counts.zero_()
+        self.flag.zero_()
+        self._images = 0
+
+    def reserve(self, batch, k):
+        """Called by the appending side before its launch: checks that ``batch`` more images of ``k`` rows fit and
+        counts them.  -> the store index of the batch's first image."""
+        first = self._images
+        if int(k) != self.k:
+            raise RuntimeError(f"Detection2DStore was made for k = {self.k} rows per image, the detector writes {k}")
+        if first + batch > self.max_images:
+            raise RuntimeError(f"Detection2DStore holds {first} of at most {self.max_images} images: "
+                               f"{batch} more do not fit")
+        self._images = first + batch
+        return first
+
+    def results(self, per_class=False, num_classes=None):
+        """THE synchronisation point -> per image the (n,6) tensor ``extract_bboxes_2d`` returns, in host memory;
+        ``per_class``: mmdet's ``bbox2result`` instead - a list of ``num_classes`` (n_c,5) float32 arrays per image,
+        rows in score order inside a class.  Raises if a NaN logit was met."""
+        n = self._images
+        counts = torch.cat([self.flag, self.counts[:n]]).cpu().numpy()
+        if counts[0] != 0:
+            raise RuntimeError("Detection2DStore: a NaN class logit was met while selecting detections")
+        rows = self.rows[:n].cpu()
+        out = [rows[i, :int(c)].clone() for i, c in enumerate(counts[1:])]
+        if not per_class:
+            return out
+        if num_classes is None:
+            raise ValueError("results(per_class=True) needs num_classes")
+        res = []
+        for r in out:
+            r = r.numpy()
+            res.append([r[r[:, 5] == c, :5].astype(np.float32) for c in range(int(num_classes))])
+        return res

@@ -5,6 +5,12 @@
                            [--tta-scales 0.9,1.0,1.1] [--tta-flip] [--tta-mode bev|3d|aligned] [--tta-nms-thr T]
                            [--gpus N]
   python -m demf_amd.infer --data-root R --frames manifest.json --checkpoint C --out results.pkl
+  python -m demf_amd.infer --model detr2d --data-root R (--ann-file F | --frames M) --checkpoint C --out results.pkl
+                           [--score-thr 0.09] [--max-per-img 100]
+
+``--model detr2d`` runs the image branch's 2D detector (``modules.Detr2D``, a stage-1 checkpoint) over the images and
+pickles mmdet's per-class ``bbox2result`` lists; no 2D metric is built, so nothing is evaluated and ``--out`` is
+required; ``--gpus``, ``--tta-*`` and ``--feature-cache`` do not apply to it.
 
 ``--frames`` runs raw RGB-D frames (``dataset.RGBDFrames``: colour image, 16-bit depth PNG, calibration) through
 ``pipeline.FramePipeline``; they carry no ground truth, so nothing is evaluated and ``--out`` is required.
@@ -58,6 +64,17 @@ def run_test(model, dataset, batch_size=8, workers=8, num_points=20000, img_scal
         raise ValueError("the given pipeline was built with another tta than run_test is asked for")
     tta = loader.pipeline.tta
     model.eval()
+    if _is_detr2d(model):
+        # the 2D detector: images alone matter (the loader still reads and prepares the points - skipping them would
+        # change its batches for the other models - and predict_into ignores them); rows into a Detection2DStore
+        if world > 1 or tta is not None:
+            raise ValueError("the 2D detector runs in one process and without test-time augmentation")
+        from .detections import Detection2DStore
+        if store is None:
+            store = Detection2DStore(max(len(dataset), 1), k=model.img_bbox_head.max_per_img, device=loader.device)
+        for batch in loader:
+            model.predict_into(store, **batch)
+        return store
     if world > 1:
         # this rank's contiguous shard into a store of the common capacity (q scenes, worst-case rows: known from
         # the model's configuration, so an empty shard allocates it too), then the ranks' stores merged in rank
@@ -79,6 +96,11 @@ def run_test(model, dataset, batch_size=8, workers=8, num_points=20000, img_scal
         for batch in loader:
             model.aug_predict_into(store, **batch, tta=tta, view_store=view_store)
     return ranks.merge_stores(store, counts) if world > 1 else store
+
+
+def _is_detr2d(model):
+    from .modules.detr2d import Detr2D
+    return isinstance(model, Detr2D)
 
 
 def _model_state(ckpt):
@@ -114,8 +136,14 @@ def parse_args(argv=None):
     p.add_argument("--workers", type=int, default=8)
     p.add_argument("--out", default=None, help="pickle the per-scene results (the reference's --out)")
     p.add_argument("--no-eval", action="store_true", help="do not evaluate (then --out is required)")
-    p.add_argument("--model", choices=("demf", "votenet"), default="demf",
-                   help="demf: DeMFVoteNet; votenet: the points-only class-agnostic baseline (modules.VoteNet)")
+    p.add_argument("--model", choices=("demf", "votenet", "detr2d"), default="demf",
+                   help="demf: DeMFVoteNet; votenet: the points-only class-agnostic baseline (modules.VoteNet); "
+                        "detr2d: the image branch's 2D detector (modules.Detr2D) from a stage-1 checkpoint - no 2D "
+                        "metric exists, so --out is required and nothing is evaluated")
+    p.add_argument("--score-thr", type=float, default=None,
+                   help="--model detr2d: keep detections with a score above this (default 0.09, the reference's filter)")
+    p.add_argument("--max-per-img", type=int, default=None,
+                   help="--model detr2d: detections selected per image before the score filter (default 100)")
     p.add_argument("--tta-scales", default=None,
                    help="test-time augmentation: comma-separated point-cloud scale ratios, e.g. 0.9,1.0,1.1")
     p.add_argument("--tta-flip", action="store_true",
@@ -142,6 +170,20 @@ def parse_args(argv=None):
             p.error(f"--tta-scales / --tta-flip: {e}")
     elif args.tta_nms_thr is not None or args.tta_mode != "bev":
         p.error("--tta-mode and --tta-nms-thr go with --tta-scales / --tta-flip")
+    if args.model == "detr2d":
+        if args.gpus is not None:
+            p.error("--model detr2d runs in one process: --gpus is not supported")
+        if args.tta is not None:
+            p.error("--model detr2d has no test-time augmentation: --tta-scales / --tta-flip are not supported")
+        if not args.out:
+            p.error("--model detr2d: no 2D metric is built, nothing is evaluated: --out is required")
+        args.no_eval = True
+        args.score_thr = 0.09 if args.score_thr is None else args.score_thr
+        args.max_per_img = 100 if args.max_per_img is None else args.max_per_img
+        if args.max_per_img < 1:
+            p.error("--max-per-img must be positive")
+    elif args.score_thr is not None or args.max_per_img is not None:
+        p.error("--score-thr and --max-per-img go with --model detr2d")
     if args.frames:
         args.no_eval = True
         if not args.out:
@@ -174,10 +216,24 @@ def main(argv=None, model=None, **loader_kwargs):
     else:
         dataset = SUNRGBDDataset(args.data_root, args.ann_file, test_mode=True)
     if model is None:
-        from .modules import DeMFVoteNet, VoteNet
-        model = VoteNet() if args.model == "votenet" else DeMFVoteNet()
+        from .modules import DeMFVoteNet, Detr2D, VoteNet
+        model = VoteNet() if args.model == "votenet" else \
+            Detr2D(max_per_img=args.max_per_img) if args.model == "detr2d" else DeMFVoteNet()
+    if (args.model == "detr2d") != _is_detr2d(model):
+        raise ValueError("--model detr2d goes with a modules.Detr2D, and only with one")
     load_checkpoint(model, args.checkpoint)
     model.cuda()
+    if args.model == "detr2d":
+        from .detections import Detection2DStore
+        model.img_bbox_head.max_per_img = args.max_per_img
+        store = run_test(model, dataset, batch_size=args.batch_size, workers=args.workers,
+                         store=Detection2DStore(max(len(dataset), 1), k=args.max_per_img, score_thr=args.score_thr),
+                         **loader_kwargs)
+        with open(args.out, "wb") as f:
+            pickle.dump(store.results(per_class=True, num_classes=model.img_bbox_head.num_classes), f)
+        print("--model detr2d: %d images written to %s; not evaluated (no 2D metric is built)"
+              % (len(store), args.out))
+        return None
     store = run_test(model, dataset, batch_size=args.batch_size, workers=args.workers, tta=args.tta,
                      **loader_kwargs)
     if ranks.rank() != 0:                       # (the merged store is on every rank; rank 0 alone reports)

@@ -94,6 +94,19 @@ class MultiheadAttention(nn.Module):
         out = self._attend(query, key, value, attn_mask, key_padding_mask)
         return identity + self.dropout_layer(self.proj_drop(out))
 
+    def _eval_kernel_ok(self, query, key, value, attn_mask, key_padding_mask):
+        """What demf_attn_fwd_eval takes: eval mode on the device, self-attention (one q | k operand, values of the
+        same positions), no masks, heads of 32 channels, at most ATTN_EVAL_MAX_Q positions, fp32, and nothing that
+        would need a backward through it.  Training mode and every other case keep the module arithmetic below."""
+        a = self.attn
+        if self.training or not query.is_cuda or key is not query or value.shape != query.shape:
+            return False
+        if attn_mask is not None or key_padding_mask is not None or query.dtype != torch.float32:
+            return False
+        if a.embed_dim // a.num_heads != 32 or not 1 <= query.shape[0] <= ops.ATTN_EVAL_MAX_Q:
+            return False
+        return not (torch.is_grad_enabled() and (query.requires_grad or value.requires_grad
+                                                 or a.in_proj_weight.requires_grad))
 
     def _attend(self, query, key, value, attn_mask, key_padding_mask):
         """torch.nn.MultiheadAttention's math (seq-first, packed in_proj) spelled out on
@@ -103,6 +116,14 @@ class MultiheadAttention(nn.Module):
         S, H = key.shape[0], a.num_heads
         Dh = E // H
         W, b = a.in_proj_weight, a.in_proj_bias
+        if self._eval_kernel_ok(query, key, value, attn_mask, key_padding_mask):
+            # inference self-attention on the device: demf_attn_fwd_eval over the packed [q | k | v] rows, batch-major
+            # (csrc/detr2d.hip) - no score tensor, no library GEMM
+            rows = lambda t: t.transpose(0, 1).reshape(B * L, E)
+            qk = ops.linear(rows(query), W[:2 * E], None if b is None else b[:2 * E])
+            v = ops.linear(rows(value), W[2 * E:], None if b is None else b[2 * E:])
+            out = ops.attn_eval(torch.cat([qk, v], 1), B, H)
+            return ops.linear(out, a.out_proj.weight, a.out_proj.bias).view(B, L, E).transpose(0, 1)
         if key is query:
             qk = ops.linear(query, W[:2 * E], None if b is None else b[:2 * E])
             q, k = qk[..., :E], qk[..., E:]

@@ -2671,3 +2671,79 @@ def meter_merge(rings, out=None):
         raise ValueError("meter_merge: out must be (rows, %d) int32" % METER_ROW_WORDS)
     _ffi.call("demf_meter_merge", int(rings.shape[0]), int(rings.shape[1]), _p(rings), _p(out), _stream())
     return out
+
+
+# --------------------------------------------------------------------------
+# Test side of the image branch's 2D detector (csrc/detr2d.hip; modules/detr2d.py)
+# --------------------------------------------------------------------------
+ATTN_EVAL_MAX_Q = _ffi.CONSTANTS["DEMF_ATTN_EVAL_MAX_Q"]
+DETR2D_MAX_CLASSES = _ffi.CONSTANTS["DEMF_DETR2D_MAX_CLASSES"]
+DETR2D_MAX_CANDIDATES = _ffi.CONSTANTS["DEMF_DETR2D_MAX_CANDIDATES"]
+DETR2D_MAX_K = _ffi.CONSTANTS["DEMF_DETR2D_MAX_K"]
+
+
+def attn_eval(qkv, B, H, scale=None, out=None):
+    """Inference self-attention (demf_attn_fwd_eval): ``qkv`` (B*Q, 3*H*Dh) = [q | k | v] packed projections ->
+    out (B*Q, H*Dh) = softmax(scale q k^T) v per (scene, head); ``scale`` defaults to 1 / sqrt(Dh).  No dropout,
+    nothing saved for a backward.  Dh = 32 and Q <= ATTN_EVAL_MAX_Q, anything else raises (DEMF_EUNSUPPORTED)."""
+    _chk(qkv, "qkv")
+    if qkv.dim() != 2 or B < 1 or H < 1 or qkv.shape[0] % B or qkv.shape[1] % (3 * H):
+        raise ValueError("attn_eval: qkv must be (B*Q, 3*H*Dh)")
+    Q, Dh = qkv.shape[0] // B, qkv.shape[1] // (3 * H)
+    if out is None:
+        out = torch.empty((B * Q, H * Dh), dtype=torch.float32, device=qkv.device)
+    _chk(out, "out")
+    if tuple(out.shape) != (B * Q, H * Dh):
+        raise ValueError("attn_eval: out must be (B*Q, H*Dh)")
+    _ffi.call("demf_attn_fwd_eval", B, H, Q, Dh, _p(qkv), float(Dh ** -0.5 if scale is None else scale), _p(out),
+              _stream())
+    return out
+
+
+def detr2d_head(hs, hidden, w_cls, b_cls, w_reg, b_reg, reference, logits=None, boxes=None):
+    """Tail of the 2D detector's last-layer branches (demf_detr2d_head): hs (R,K) decoder output rows, hidden (R,K)
+    the box branch after its two Linear + ReLU, w_cls (C,K), w_reg (4,K), reference (Q,2) the queries' reference
+    points (row r reads reference[r % Q]) -> logits (R,C), boxes (R,4) normalised (cx, cy, w, h)."""
+    for n, t in (("hs", hs), ("hidden", hidden), ("w_cls", w_cls), ("b_cls", b_cls), ("w_reg", w_reg),
+                 ("b_reg", b_reg), ("reference", reference)):
+        _chk(t, n)
+    R, K = hs.shape
+    C = w_cls.shape[0]
+    if tuple(hidden.shape) != (R, K) or tuple(w_cls.shape) != (C, K) or tuple(w_reg.shape) != (4, K) or \
+            b_cls.numel() != C or b_reg.numel() != 4 or reference.dim() != 2 or reference.shape[1] != 2 or \
+            reference.shape[0] < 1 or R % reference.shape[0]:
+        raise ValueError("detr2d_head: hs / hidden (R,K), w_cls (C,K), w_reg (4,K), reference (Q,2) with Q | R expected")
+    if logits is None:
+        logits = torch.empty((R, C), dtype=torch.float32, device=hs.device)
+    if boxes is None:
+        boxes = torch.empty((R, 4), dtype=torch.float32, device=hs.device)
+    _chk(logits, "logits")
+    _chk(boxes, "boxes")
+    if tuple(logits.shape) != (R, C) or tuple(boxes.shape) != (R, 4):
+        raise ValueError("detr2d_head: logits (R,C) and boxes (R,4) expected")
+    _ffi.call("demf_detr2d_head", R, C, K, _p(hs), _p(hidden), _p(w_cls), _p(b_cls), _p(w_reg), _p(b_reg),
+              _p(reference), int(reference.shape[0]), _p(logits), _p(boxes), _stream())
+    return logits, boxes
+
+
+def detr2d_select(logits, boxes, meta, k, thr, rescale, rows, counts, flag):
+    """Per-image top-k + decode + threshold of the 2D detector (demf_detr2d_select), one launch, no host sync:
+    logits (B,Q,C), boxes (B,Q,4) normalised cxcywh, meta (B,6) = [img h, img w, scale_factor x4] on the device ->
+    rows (B,k,6) = [x1, y1, x2, y2, score, class] in the order (logit descending, index q*C + c ascending) for the
+    places with score > thr (thr < 0: all), zeros behind; counts (B) int32; flag (1) int32, bit 0 = a NaN logit."""
+    _chk(logits, "logits")
+    _chk(boxes, "boxes")
+    _chk(meta, "meta")
+    _chk(rows, "rows")
+    _chk(counts, "counts", torch.int32)
+    _chk(flag, "flag", torch.int32)
+    if logits.dim() != 3:
+        raise ValueError("detr2d_select: logits must be (B,Q,C)")
+    B, Q, C = logits.shape
+    k = int(k)
+    if tuple(boxes.shape) != (B, Q, 4) or tuple(meta.shape) != (B, 6) or tuple(rows.shape) != (B, k, 6) or \
+            counts.numel() != B or flag.numel() < 1:
+        raise ValueError("detr2d_select: boxes (B,Q,4), meta (B,6), rows (B,k,6), counts (B) and a flag word expected")
+    _ffi.call("demf_detr2d_select", B, Q, C, k, _p(logits), _p(boxes), _p(meta), int(bool(rescale)), float(thr),
+              _p(rows), _p(counts), _p(flag), _stream())
+    return rows, counts

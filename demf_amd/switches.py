@@ -34,6 +34,8 @@ TABLE = {
     "DEMF_MIOPEN_SEARCH": (0, "MIOpen exhaustive search (library path only)"),
     "DEMF_ENC_PRE_ADD": (0, "encoder: query + pos added ahead of the projection"),
     "DEMF_ENC_SPLIT_LN": (1, "encoder FFN: LayerNorm as its own launch"),
+    "DEMF_DETR2D_FUSED": (1, "2D detector: decoder and head on the row-GEMM / attention / selection kernels"),
+    "DEMF_DETR2D_VALUE_ONE": (1, "2D detector: the six layers' value projections of the memory as one launch"),
     "DEMF_AR_OVERLAP": (0, "all-reduce overlapped with the backward"),
     "DEMF_GRAPH_UPDATE": (1, "optimizer update inside the captured step"),
     "DEMF_GRAPH_ALLREDUCE": (0, "all-reduce inside the captured step"),

@@ -1314,6 +1314,46 @@ DEMF_INTERNAL int demf_groupnorm_nhwc_f32(int B, int HW, int C, int G, float eps
                             const float* beta, double* sums, float* y, long long y_batch_stride,
                             demf_stream_t stream);
 
+/* ------------------------------------------------------------------ *
+ * Test side of the image branch's 2D detector (csrc/detr2d.hip): the Deformable-DETR decoder and head of
+ * configs/deformdetr/imvotenet_image.py:21-80, which ImVoteNet_Deformdetr.extract_bboxes_2d
+ * (demf/modeling/detectors/imvotenet_deform.py:188-248) runs as img_bbox_head.simple_test.
+ * ------------------------------------------------------------------ */
+#define DEMF_ATTN_EVAL_MAX_Q 512          /* K and V of one (scene, head) stay in LDS */
+#define DEMF_DETR2D_MAX_CLASSES 32
+#define DEMF_DETR2D_MAX_CANDIDATES 8192   /* Q * C scores of one image: 64-bit keys in 64 KB of LDS */
+#define DEMF_DETR2D_MAX_K 1024
+
+/* Inference self-attention for any query count: out[b, q, h] = softmax(scale * q_h k_h^T) v_h from the packed
+ * projections qkv (B*Q, 3*H*Dh) = [q | k | v] -> out (B*Q, H*Dh).  No dropout, no statistics, the scores are never
+ * stored.  nn.MultiheadAttention in eval mode inside mmcv's DetrTransformerDecoderLayer as the 2D detector's decoder
+ * runs it over its 300 learned queries (configs/deformdetr/imvotenet_image.py:52-57; demf_attn_core_fwd is built
+ * for the fusion layer's Q = 256).  Dh = 32 and 1 <= Q <= DEMF_ATTN_EVAL_MAX_Q: DEMF_EUNSUPPORTED otherwise.
+ * Compute mode 1 rounds q, k, v and the probabilities to bf16 where they become operands; modes 0 / 2 are fp32 FMAs. */
+DEMF_INTERNAL int demf_attn_fwd_eval(int B, int H, int Q, int Dh, const float* qkv, float scale, float* out,
+                       demf_stream_t stream);
+/* Tail of the last decoder layer's branches (mmdet DeformableDETRHead.forward, which
+ * img_bbox_head.simple_test reaches at imvotenet_deform.py:210): logits (R,C) = hs (R,K) . w_cls (C,K)^T + b_cls and
+ * boxes (R,4) = sigmoid(hidden (R,K) . w_reg (4,K)^T + b_reg [+ inverse_sigmoid(reference) on columns 0, 1]) -
+ * normalised (cx, cy, w, h); hidden = the box branch after its two Linear + ReLU layers; row r reads
+ * reference[r % ref_rows] (ref_rows, 2); inverse_sigmoid with mmdet's eps = 1e-5.  fp32 FMAs in every compute mode.
+ * C <= DEMF_DETR2D_MAX_CLASSES, K % 4 == 0, K <= 1024. */
+DEMF_INTERNAL int demf_detr2d_head(int R, int C, int K, const float* hs, const float* hidden, const float* w_cls,
+                     const float* b_cls, const float* w_reg, const float* b_reg, const float* reference,
+                     int ref_rows, float* logits, float* boxes, demf_stream_t stream);
+/* mmdet DeformableDETRHead._get_bboxes_single for a whole batch + the score filter of extract_bboxes_2d
+ * (imvotenet_deform.py:181-186,210-230), one launch, nothing read back: per image the k best of the Q*C candidates
+ * in the order (logit descending, flat index q*C + c ascending) - one of the orders torch.topk over the sigmoid
+ * scores may return -, label = index % C, query = index / C, boxes (B*Q,4) cxcywh -> xyxy, x * img w, y * img h,
+ * clamped to the image, divided by the four scale factors when rescale != 0; meta (B,6) = [img h, img w,
+ * scale_factor x4].  rows (B,k,6) = [x1, y1, x2, y2, score, class] for the places with sigmoid(logit) > thr (a prefix
+ * of the order; thr < 0: all min(k, Q*C) places), zeros behind them; counts (B) = their number.  NaN logits order
+ * after every number and set bit 0 of *flag.  Q*C <= DEMF_DETR2D_MAX_CANDIDATES, k <= DEMF_DETR2D_MAX_K:
+ * DEMF_EUNSUPPORTED otherwise. */
+DEMF_INTERNAL int demf_detr2d_select(int B, int Q, int C, int k, const float* logits, const float* boxes,
+                       const float* meta, int rescale, float thr, float* rows, int* counts, int* flag,
+                       demf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
