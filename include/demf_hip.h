@@ -686,8 +686,10 @@ DEMF_INTERNAL int demf_vote_loss_fwd(int B, int S, int N, int gt_per_seed, float
  * (config demf_votenet.py:79-85: H=8, L=4, P=2, Dh=32).
  * value (B,S,H,Dh), spatial_shapes (L,2) i64 (h,w), level_start_index (L) i64,
  * sampling_loc (B,Q,H,L,P,2) (x,y in [0,1]), attn_weight (B,Q,H,L,P)
- * -> out (B,Q,H*Dh).  Bilinear, align_corners=False, zero padding.  Dh must be
- * a multiple of 4 and <= 256.                                                */
+ * -> out (B,Q,H*Dh).  Bilinear, align_corners=False, zero padding.  Any Dh >= 1
+ * with S*H*Dh < 2^31, L <= 8, P >= 1.  Dh = 4 G with G in {1,2,4,8,16,32,64}
+ * (Dh <= 256) and 16-byte aligned value / out run G lanes per (b,q,h); every
+ * other Dh or alignment runs one thread per (b,q,h), serial over the channels. */
 int demf_msda_fwd_f32(int B, int S, int H, int Dh, int L, int Q, int P,
                       const float* value, const int64_t* spatial_shapes,
                       const int64_t* level_start_index, const float* sampling_loc,

@@ -191,8 +191,9 @@ def test_rows_gemm_epilogues_vs_fp64(planes):
 
 def test_msda_raw_matches_the_composed_operator():
     """demf_msda_fwd_raw_f32 (softmax + sampling locations inside, value rows with a pitch) against
-    MultiScaleDeformableAttnFunction on explicitly computed locations / weights - both its kernels (one wave per
-    query, and 8 lanes per (query, head) via DEMF_MSDA_RAW_LANES in a fresh process is covered by the encoder test)."""
+    MultiScaleDeformableAttnFunction on explicitly computed locations / weights.  H = 8 with even, aligned operands:
+    this runs the one-wave-per-query kernel.  The form with 8 lanes per (query, head) is run, against float64, by
+    tests/test_gpu_msda_edges.py::test_raw_entry (the lane_* cases)."""
     from demf_amd import ops
     g = torch.Generator().manual_seed(5)
     B, H, Dh, L = 2, 8, 32, 4
